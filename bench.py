@@ -15,16 +15,20 @@ Workloads (BASELINE.json configs; --workload):
   ngo100k              config[1]: 100k rays, Ngo model, adaptive RK45, maxsteps=512, outputper=8 (compute-bound).
   scattered825k        config[4]: 1M rays, scattered model on the 825k-sample set, maxsteps=64, outputper=8.
   interp_igrf200k / interp_t04_64k   config[2]'s set and grid with --use_igrf=1 / --use_tsyganenko=1 (200k / 64k rays).
-The default invocation additionally times one short run of the other configs (`other_configs`), so that every
-BASELINE config is driver-timed.  Inputs are synthetic (seeded launch set + analytic plasmasphere)
-and resident in HBM before the timed region starts.
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last
+timed step computed (dump_outputs).  --full adds everything else this script measures or checks, after the timed
+steps: one short run of each other config (`other_configs`, so that every BASELINE config is driver-timed), the CLI end
+to end, the live counter passes, the stream-copy rate, the pack cost, the damping leg, the CPU baselines, the pipelined
+N>1 pass and rows_checksum.  Inputs are synthetic (seeded launch set + analytic plasmasphere) and
+resident in HBM before the timed region starts.
 
 Multi-GPU: every step goes through stanford_raytracer_amd.parallel.trace_sharded (shard -> trace -> pack ->
 variable-length gather), the same function the gloo and 2-rank GPU tests run.
 
 Roofline (N=1): `achieved` = bytes the kernel moved through the L2's fabric side per launch (rocprofv3 PMC,
 FETCH_SIZE x2 + WRITE_SIZE, collected LIVE by two child passes of this script under rocprofv3 before this process
-touches the GPU) / the kernel's HIP-event duration in the timed region; `frac` = achieved / 8 TB/s.  The SURVEY 8d
+touches the GPU in a --full run; a plain run reads profiles/traffic_<workload>.json when it was collected for these
+kernel sources) / the kernel's HIP-event duration in the timed region; `frac` = achieved / 8 TB/s.  The SURVEY 8d
 algorithmic figure (44 lookups x 2 KiB per accepted step) is reported beside it as `algorithmic_GBs` -- it is NOT a
 fraction of anything: the 7-point stencil shares one block, so the kernel moves far fewer bytes than that figure.
 """
@@ -81,13 +85,21 @@ def parse_args(argv=None):
     ap.add_argument("--grid", type=int, default=0, help="override grid nodes per axis (interp)")
     ap.add_argument("--maxsteps", type=int, default=0)
     ap.add_argument("--points", type=int, default=0, help="override sample count (scattered)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample duration (0=skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well: live PMC traffic, the other BASELINE configs, "
+                         "the CLI end to end, the stream-copy rate, the pack cost, the damping leg, the CPU baselines, the "
+                         "pipelined multi-GPU pass, rows_checksum (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=None,
+                    help="target CPU-baseline sample duration (0=skip; default 15 with --full, else 0)")
     ap.add_argument("--use-igrf", type=int, default=0, choices=[0, 1], help="IGRF main field instead of the dipole (driver flag --use_igrf)")
     ap.add_argument("--use-tsyganenko", type=int, default=0, choices=[0, 1],
                     help="add the T04_s external field (driver flag --use_tsyganenko; PARMOD = Pdyn 4, Dst -30, By 1, Bz -5, W .1-.3)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: trace only (no pack, no gather)")
-    ap.add_argument("--damping-rays", type=int, default=100_000,
-                    help="rays whose kept rows get the damping post-pass after the timed region (N=1 only; 0 = skip)")
+    ap.add_argument("--damping-rays", type=int, default=None,
+                    help="rays whose kept rows get the damping post-pass after the timed region (N=1 only; 0 = skip; "
+                         "default 100000 with --full, else 0)")
     ap.add_argument("--refill", type=int, default=0)
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams the steps alternate on at N=1 (1 = strictly serial, the default: kernel time == step "
@@ -98,11 +110,16 @@ def parse_args(argv=None):
     ap.add_argument("--traffic", default="auto", choices=["auto", "live", "file", "off"],
                     help="where roofline.traffic comes from: live = two rocprofv3 PMC child passes of this script "
                          "(FETCH_SIZE, WRITE_SIZE) before the timed run; file = profiles/traffic_<workload>.json if it was "
-                         "collected for these kernel sources; auto = live at N=1 when rocprofv3 exists, else file")
+                         "collected for these kernel sources; auto = live in a --full run at N=1 when rocprofv3 exists, else file")
     ap.add_argument("--other-configs", type=int, default=-1, choices=[-1, 0, 1],
-                    help="time one short run of the other BASELINE configs as well (-1 = only in the default invocation)")
+                    help="time one short run of the other BASELINE configs as well (-1 = only in a --full run of the default workload)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # internal: one bare launch under rocprofv3
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 15.0 if args.full else 0.0
+    if args.damping_rays is None:
+        args.damping_rays = 100_000 if args.full else 0
+    return args
 
 
 # --------------------------------------------------------------------------------------------- provenance
@@ -165,7 +182,7 @@ def pmc_pass(counters, child_args, timeout=420):
 
 
 def child_args_for(args, workload, rays=0):
-    a = ["--workload", workload, "--steps", "1", "--warmup", "0", "--ray-order", str(args.ray_order)]
+    a = ["--workload", workload, "--steps", "1", "--warmup", "0", "--ray-order", str(args.ray_order), "--full"]
     if rays or args.rays:
         a += ["--rays", str(rays or args.rays)]
     for k, v in (("--grid", args.grid), ("--maxsteps", args.maxsteps), ("--points", args.points), ("--refill", args.refill)):
@@ -269,9 +286,10 @@ def field_of(args, W):
     return W.get("field", (args.use_igrf, args.use_tsyganenko))
 
 
-def run_workload(ctx, name, steps, warmup, rays_override=0, nstream=1, keep=False):
+def run_workload(ctx, name, steps, warmup, rays_override=0, nstream=1, keep=False, dump=None):
     """W untimed + K timed steps of one workload on this rank's shard.  Returns a dict (all ranks; whole-job numbers
-    are reduced over ranks) -- or, with keep=True, also the DeviceBatch so the caller can post-process its rows."""
+    are reduced over ranks) -- or, with keep=True, also the DeviceBatch so the caller can post-process its rows.
+    dump: directory that receives the last timed step's outputs (dump_outputs)."""
     from stanford_raytracer_amd import api, parallel, workloads as wl
     from stanford_raytracer_amd.device_batch import DeviceBatch
 
@@ -335,6 +353,13 @@ def run_workload(ctx, name, steps, warmup, rays_override=0, nstream=1, keep=Fals
     if not gather:
         for i in range(max(0, steps - LAG), steps):
             kernel_ms[i] = model.launch_ms(steps - 1 - i)
+    if dump and rank == 0 and steps:
+        if gather:  # what rank 0 holds after the last step's gather: the whole launch set, rows packed
+            packed, nr_all, st_all = last_gathered[0]
+            dump_outputs(dump, torch, nr_all, st_all, p.outputper, batch.slots, packed=packed)
+        else:
+            last = batch.out[(steps - 1) % nstream]
+            dump_outputs(dump, torch, last["nrows"], last["stop"], p.outputper, batch.slots, rows=last["rows"])
     c = np.sum([x.cpu().numpy() for x in cnts], axis=0) if steps else np.zeros(4, dtype=np.int64)
     red = np.array([elapsed, float(np.mean(kernel_ms)) if steps else 0.0,
                     float(np.mean([t.get("gather_s", 0.0) for t in tms])) if steps else 0.0,
@@ -360,12 +385,13 @@ def run_workload(ctx, name, steps, warmup, rays_override=0, nstream=1, keep=Fals
         "stop": o["stop"].cpu().numpy(), "nrows": o["nrows"].cpu().numpy(),
         "launch": (pos0[lo:hi], dir0[lo:hi], w0[lo:hi]), "field": fld,
     }
-    if gather and rank == 0 and last_gathered[0] is not None:
+    # (--full only: the checksum, the pack cost and the latency floor take device work of their own after the timed steps)
+    if args.full and gather and rank == 0 and last_gathered[0] is not None:
         # what rank 0 holds after the last step's gather, as a number a one-GPU run of the same launch set must reproduce
         pk, nr_all, st_all = last_gathered[0]
         res["rows_checksum"] = rows_checksum(torch, pk, nr_all, st_all)
         res["gathered_rows"] = int(pk.shape[0])
-    if world == 1 and kind == "interp" and steps:
+    if args.full and world == 1 and kind == "interp" and steps:
         # the fixed cost the multi-GPU step adds on every rank: packing the kept rows of this launch (srt_pack_rows_device)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         parallel.pack_rows_device(o["rows"], o["nrows"], p.outputper, slot=0)  # (allocates the reused buffer)
@@ -379,7 +405,7 @@ def run_workload(ctx, name, steps, warmup, rays_override=0, nstream=1, keep=Fals
         res["rows_checksum"] = rows_checksum(torch, pk[:int(off[-1])], o["nrows"], o["stop"])
         res["gathered_rows"] = int(off[-1])
         parallel.release_pack_buffers(dev)
-    if world == 1 and kind == "ngo" and steps and hi > lo:
+    if args.full and world == 1 and kind == "ngo" and steps and hi > lo:
         # what bounds this launch from below: its longest rays alone (<= 8 rays = one wave in tail mode, srt_models.hpp):
         # their sequential attempts x the tail-mode trip time
         nr = res["nrows"]
@@ -411,6 +437,46 @@ def rows_checksum(torch, packed, nrows, stop):
         return int((v * wgt).sum().item())
     tot = (wsum(packed) * 3 + wsum(nrows) * 5 + wsum(stop) * 7) & 0xFFFFFFFFFFFFFFFF
     return "%016x" % tot
+
+
+DUMP_RAYS = 1 << 20         # --dump-outputs: row counts and stop codes of at most this many rays (16 MB)
+DUMP_ROWS_BYTES = 32 << 20  # ... and the kept rows of as many rays as fit here, at most DUMP_ROW_RAYS
+DUMP_ROW_RAYS = 8192
+
+
+def dump_sample(n, k, seed):
+    """Indices of a fixed, seeded sample of k of n rays, in ray order (all n when n <= k)."""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(outdir, torch, nrows, stop, outputper, slots, rows=None, packed=None):
+    """--dump-outputs: what one step of the timed path hands its caller, as .npy files (at most 49 MB in all).
+    rays.npy lists the rays (all of them up to DUMP_RAYS, else a seeded sample) whose nrows.npy and stop.npy follow (float32:
+    exact); rows_rays.npy lists a seeded sample of rays whose kept rows rows.npy holds (float64 [rays, slots, 20], zero in
+    the slots beyond a ray's kept rows, which the library leaves unwritten).  The rows come as traced (rows [n, slots, 20])
+    or as gathered (packed [kept rows, 20] in ray order)."""
+    from stanford_raytracer_amd import api, parallel
+
+    os.makedirs(outdir, exist_ok=True)
+    nr = nrows.cpu().numpy().astype(np.int64)
+    st = stop.cpu().numpy()
+    idx = dump_sample(len(nr), DUMP_RAYS, 1)
+    ridx = dump_sample(len(nr), max(1, min(DUMP_ROW_RAYS, DUMP_ROWS_BYTES // (slots * api.ROW * 8))), 2)
+    kept = parallel.kept_rows(nr, outputper, slots)
+    mask = np.arange(slots)[None, :] < kept[ridx][:, None]
+    if packed is not None:
+        first = np.concatenate([[0], np.cumsum(kept)])[ridx]
+        sel = torch.from_numpy((first[:, None] + np.arange(slots)[None, :])[mask]).to(packed.device)
+        sample = np.zeros((len(ridx), slots, api.ROW))
+        sample[mask] = packed[sel].cpu().numpy()
+    else:
+        sample = rows[torch.from_numpy(ridx).to(rows.device)].cpu().numpy()
+        sample[~mask] = 0.0
+    for name, a in (("rays", idx.astype(np.float64)), ("nrows", nr[idx].astype(np.float32)), ("stop", st[idx].astype(np.float32)),
+                    ("rows_rays", ridx.astype(np.float64)), ("rows", sample)):
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def pipelined_pass(ctx, name, rays_override=0, steps=3):
@@ -493,7 +559,7 @@ def main():
         sys.exit(2)
     default_invocation = (args.workload == "interp256" and not (args.rays or args.grid or args.maxsteps or args.use_igrf
                                                                 or args.use_tsyganenko))
-    want_other = args.other_configs == 1 or (args.other_configs == -1 and default_invocation and not args.pmc_child)
+    want_other = args.other_configs == 1 or (args.other_configs == -1 and args.full and default_invocation and not args.pmc_child)
     khash = kernel_source_hash()
 
     # ---- 0. counter passes: child processes under rocprofv3, BEFORE this process touches the GPU -------------------
@@ -502,7 +568,7 @@ def main():
     if args.pmc_child or world > 1:
         mode = "off" if args.pmc_child else ("file" if mode in ("auto", "live") else mode)
     elif mode == "auto":
-        mode = "live" if shutil.which("rocprofv3") else "file"
+        mode = "live" if (args.full and shutil.which("rocprofv3")) else "file"
     if mode == "live":
         traffic, traffic_note = live_traffic(args, args.workload)
         if want_other:  # config[1]: fp64 VALU mix of one launch; config[4]: fabric bytes of a 100k-ray launch
@@ -545,7 +611,8 @@ def main():
     ctx = Ctx(args, torch, dev, dist, rank, world)
 
     progress("%s: %d warm-up + %d timed steps on %d GPU(s)" % (args.workload, args.warmup, args.steps, world))
-    res = run_workload(ctx, args.workload, args.steps, args.warmup, rays_override=args.rays, nstream=args.streams, keep=True)
+    res = run_workload(ctx, args.workload, args.steps, args.warmup, rays_override=args.rays, nstream=args.streams, keep=True,
+                       dump=args.dump_outputs)
     if args.pmc_child:  # the parent (pmc_pass) reads this line from the child's stdout
         print(json.dumps({"pmc_child": {"accepted": res["accepted"], "kernel_ms": res["kernel_ms_rank0"], "rays": res["rays_this_rank"]}}))
         return
@@ -556,7 +623,7 @@ def main():
 
     # ---- N > 1: the same steps with the pack + gather of step k behind the trace of step k + 1 (outside the timed region) --
     pipe = None
-    if world > 1 and res["gather"]:
+    if args.full and world > 1 and res["gather"]:
         pipe = pipelined_pass(ctx, args.workload, rays_override=args.rays)
         if pipe.get("ms_per_step") is not None:
             pipe["gather_ms_exposed"] = pipe["ms_per_step"] - res["kernel_ms"]
@@ -578,7 +645,7 @@ def main():
         other["cli_end_to_end"] = cli_end_to_end(ctx, res)
 
     stream_gbs = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # the box's own streaming rate ("measure a device-to-device copy and use THAT as 100 %"): read +
         # write bytes of a 2 GiB copy, outside the timed region
         try:

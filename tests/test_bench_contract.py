@@ -58,3 +58,41 @@ def test_workload_table_matches_baseline_json():
     assert "4M rays" in cfgs[3] and bench.WORKLOADS["interp4m"]["rays"] == 4_000_000 and bench.WORKLOADS["interp4m"]["scaling"] == "strong"
     assert "1M rays" in cfgs[4] and bench.WORKLOADS["scattered825k"]["rays"] == 1_000_000
     assert bench.parse_args([]).workload == "interp256" and bench.parse_args([]).streams == 1
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    plain, full = bench.parse_args([]), bench.parse_args(["--full"])
+    assert not plain.full and plain.cpu_seconds == 0 and plain.damping_rays == 0 and plain.dump_outputs is None
+    assert full.full and full.cpu_seconds == 15.0 and full.damping_rays == 100_000
+    assert bench.parse_args(["--cpu-seconds", "3", "--damping-rays", "7"]).cpu_seconds == 3.0
+    assert "--full" in bench.child_args_for(plain, "ngo100k")   # the counter passes' children run as they always did
+
+
+def test_dump_outputs_same_from_traced_and_from_gathered_rows(tmp_path):
+    """--dump-outputs writes the same files from one GPU's traced rows [n, slots, 20] and from rank 0's gathered packed rows;
+    a seeded sample of a larger launch, zero beyond each ray's kept rows, within its size budget."""
+    import torch
+
+    from stanford_raytracer_amd import parallel
+
+    n, slots, outputper = 9000, 5, 4
+    rng = np.random.default_rng(0)
+    rows = torch.from_numpy(rng.normal(size=(n, slots, 20)))
+    nrows = torch.from_numpy(rng.integers(0, slots * outputper + 3, n).astype(np.int32))
+    stop = torch.from_numpy(rng.integers(0, 7, n).astype(np.int32))
+    packed, _ = parallel.pack_rows_torch(rows, nrows, outputper)
+    bench.dump_outputs(str(tmp_path / "a"), torch, nrows, stop, outputper, slots, rows=rows)
+    bench.dump_outputs(str(tmp_path / "b"), torch, nrows, stop, outputper, slots, packed=packed)
+    total = 0
+    for name in ("rays", "nrows", "stop", "rows_rays", "rows"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert total < 64 << 20
+    ridx = np.load(tmp_path / "a" / "rows_rays.npy").astype(np.int64)
+    assert len(ridx) == bench.DUMP_ROW_RAYS and np.all(np.diff(ridx) > 0)
+    kept = parallel.kept_rows(nrows.numpy().astype(np.int64), outputper, slots)[ridx]
+    got = np.load(tmp_path / "a" / "rows.npy")
+    for j in (0, 1, len(ridx) - 1):
+        assert np.array_equal(got[j, :kept[j]], rows.numpy()[ridx[j], :kept[j]]) and not got[j, kept[j]:].any()
+    assert np.array_equal(np.load(tmp_path / "a" / "nrows.npy"), nrows.numpy().astype(np.float32))

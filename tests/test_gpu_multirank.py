@@ -216,12 +216,14 @@ def test_rccl_branch_world_size_one(pipelined):
     assert np.array_equal(packed2.view(np.uint64), pt.cpu().numpy().view(np.uint64))
 
 
-def _run_bench(nranks, port, rays=6007):
+def _run_bench(nranks, port, dump, rays=6007):
     import json
     import subprocess
 
+    # --full: rows_checksum and the pipelined pass are measured beyond the headline
     args = ["--gpus", str(nranks), "--steps", "2", "--warmup", "1", "--workload", "interp4m", "--rays", str(rays), "--grid", "24",
-            "--maxsteps", "96", "--traffic", "off", "--other-configs", "0", "--cpu-seconds", "0", "--damping-rays", "0"]
+            "--maxsteps", "96", "--traffic", "off", "--other-configs", "0", "--cpu-seconds", "0", "--damping-rays", "0", "--full",
+            "--dump-outputs", str(dump)]
     cmd = [sys.executable]
     if nranks > 1:
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nranks), "--master-addr", "127.0.0.1",
@@ -235,7 +237,7 @@ def _run_bench(nranks, port, rays=6007):
     return json.loads(lines[0])
 
 
-def test_three_rank_rehearsal_through_bench_py():
+def test_three_rank_rehearsal_through_bench_py(tmp_path):
     """`bench.py --gpus N` as the driver launches it (python -m torch.distributed.run, one process per rank, rendezvous on
     127.0.0.1), rehearsed on the one card: 3 ranks (the box's process guard kills a run with more than 6 processes on the GPU:
     this test runner and the launcher's agent are two of them -- a 5-rank version of this test was killed at 7) with the gloo
@@ -244,9 +246,10 @@ def test_three_rank_rehearsal_through_bench_py():
     Through bench.py's own code: parallel.trace_sharded (counts all_gather, grouped send / recv of the packed rows to rank 0),
     the barrier-bracketed timed region, the max-over-ranks reduction, the pipelined pass.  The printed line must name 3 GPUs,
     carry the multi_gpu fields, and its rows_checksum -- a position-weighted sum over the bits of every gathered row, row count
-    and stop code -- must equal the one-GPU run's of the same launch set."""
-    one = _run_bench(1, 0)
-    many = _run_bench(3, _free_port())
+    and stop code -- must equal the one-GPU run's of the same launch set, and so must the outputs --dump-outputs writes
+    (rank 0's gathered rows against the one-GPU run's traced rows)."""
+    one = _run_bench(1, 0, tmp_path / "one")
+    many = _run_bench(3, _free_port(), tmp_path / "many")
     assert one["n_gpus"] == 1 and many["n_gpus"] == 3 and many["scaling"] == "strong"
     assert many["config"]["total_rays"] == 6007 and many["config"]["rays_per_gpu"] == 2003
     mg = many["multi_gpu"]
@@ -262,3 +265,8 @@ def test_three_rank_rehearsal_through_bench_py():
     rows0 = mg["gather_bytes_into_rank0"]
     assert 0 < rows0 < many["detail"]["packed_rows"] * 160 + 6007 * 8
     assert many["value"] > 0 and many["steps"] == 2 and many["warmup"] == 1
+    for name in ("rays", "nrows", "stop", "rows_rays", "rows"):
+        a, b = np.load(tmp_path / "one" / (name + ".npy")), np.load(tmp_path / "many" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, name
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), name
+    assert np.load(tmp_path / "one" / "nrows.npy").shape == (6007,) and np.load(tmp_path / "one" / "rows.npy").any()
