@@ -13,7 +13,8 @@ namespace srt {
 // Build with -DSRT_TRIP_TIMING for a cycle breakdown of one attempt trip in block 0 (srt_trip_cycles[], printed after a trace
 // launch when the environment variable SRT_TRIP_TIMING is set): 0 stencil densities inside the stages, 1 rest of evalrhs,
 // 2 end-point stencil densities, 3 error term, 4 root re-projection, 5 end-point right-hand side, 6 bookkeeping, 7 trips,
-// 8 trips with <= 8 active lanes, 9 loop top (stop tests, refill), 10 stage bookkeeping.
+// 8 trips with <= 8 active lanes, 9 loop top (stop tests, refill), 10 stage bookkeeping; interp model (counts, not cycles):
+// 14 lane-lookups whose rows were not resident in the ring, 15 wave-lookups that re-staged any rows.
 #ifdef SRT_TRIP_TIMING
 #define SRT_TT_BEGIN() __builtin_amdgcn_sched_barrier(0); unsigned long long tt0_ = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0)
 #define SRT_TT(slot)                                                                                   \
@@ -354,6 +355,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
   __shared__ __attribute__((aligned(16))) double tile[USE_LDS ? WaveBudget<M>::LDS_DOUBLES : 2];
   double *lds = USE_LDS ? tile : nullptr;
   bind_scratch(m, lds, a.scratch, a.scratch2);
+  if (USE_LDS) tile_reset(m, lds);
   const TraceParams &P = a.p;
   const int lane = threadIdx.x;
   const Tableau &tab = FIXED ? TAB_RK4 : TAB_RKF45;
@@ -756,6 +758,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
   const Common &cm = *cp;
   __shared__ __attribute__((aligned(16))) double tile[USE_LDS ? WaveBudget<M>::LDS_DOUBLES : 2];
   bind_scratch(m, USE_LDS ? tile : nullptr, scratch);
+  if (USE_LDS) tile_reset(m, tile);
   long long i = (long long)blockIdx.x * WAVE + threadIdx.x;
   long long j = i < n ? i : n - 1;
   double st[6] = {x[3 * j], x[3 * j + 1], x[3 * j + 2], k[3 * j], k[3 * j + 1], k[3 * j + 2]};
@@ -794,6 +797,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
   const Common &cm = *cp;
   __shared__ __attribute__((aligned(16))) double tile[USE_LDS ? WaveBudget<M>::LDS_DOUBLES : 2];
   bind_scratch(m, USE_LDS ? tile : nullptr, scratch);
+  if (USE_LDS) tile_reset(m, tile);
   long long i = (long long)blockIdx.x * WAVE + threadIdx.x;
   long long j = i < n ? i : n - 1;
   double st[6];

@@ -18,6 +18,15 @@ constexpr int UNIT_BYTES = WAVE * 128;
 constexpr int RING = 4;
 constexpr int TILE_PAD_BYTES = 2048;
 constexpr int TILE_DOUBLES = (RING * UNIT_BYTES + TILE_PAD_BYTES) / 8;
+// Residency header of the ring, at the front of the head room (no DMA writes there: only the biased base addresses of
+// the loads point into it).  RES_CELL: int[64], the cell whose rows lane j's row slots hold; RES_STATE: int[64], which
+// species the ring holds (RING_*; the same value in every lane's word, so that one address serves both).
+constexpr int RES_CELL_BYTES = 0;
+constexpr int RES_STATE_BYTES = WAVE * 4;
+constexpr int RES_END_BYTES = RES_STATE_BYTES + WAVE * 4;
+constexpr int MAX_UNIT_IMM = 384; // largest immediate of an LDS-DMA load (plane 3 of a species)
+static_assert(RES_END_BYTES <= TILE_PAD_BYTES - MAX_UNIT_IMM, "the header must lie below every biased DMA base");
+enum RingState : int { RING_INVALID = 0, RING_HOLDS_FIRST = 1, RING_HOLDS_LAST = 2 };
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 #ifdef SRT_TRIP_TIMING
@@ -42,6 +51,9 @@ __device__ __forceinline__ void bind_scratch(const M &, double *, double *, doub
 // A lane of the trace kernel has just been given a new ray (the scattered model forgets the lane's candidate block).
 template <class M>
 __device__ __forceinline__ void new_ray_hook(const M &, double *, bool) {}
+// A kernel's LDS tile holds nothing yet (the interp model keeps the last staged species in its ring across calls).
+template <class M>
+__device__ __forceinline__ void tile_reset(const M &, double *) {}
 // What the cooperative kernels (trace, gradients, RK step) reserve per wave for a model: LDS (in doubles) and the waves per
 // SIMD the kernel is compiled for (1: all 512 registers of a lane; the scattered model specialises this: srt_scattered.hpp).
 template <class M>
@@ -361,8 +373,9 @@ struct NgoModel {
 // 2048 B per lookup that the reference gathers from 8 arrays x 8 corners.  A lookup then is one
 // contiguous block read plus a polynomial evaluation.  Per wave the blocks of all 64 lanes stream through a
 // ring of four 8-KiB LDS buffers, one k-plane (128 B per lane) of one species at a time, by LDS-DMA with a
-// lookahead of three units, and every lane evaluates all its stencil points from each unit (see
-// InterpModel::density_stencil).
+// lookahead of four units, and every lane evaluates all its stencil points from each unit.  The ring holds
+// exactly one species of every lane's block; the species it ends with stays there for the next lookup, which
+// starts with it (see InterpModel::density_stencil).
 struct Axis {
   double min, del, rdel; // rdel = 1/del: only for the first guess of the cell search
   int n;
@@ -454,12 +467,13 @@ struct InterpModel {
   // 16-B bank slots (row parity = (j>>3)&1 selects the half of the 256-B bank row): conflict-free.
   // Filled by LDS-DMA: instruction t of a unit writes 1 KiB = row slots 8t..8t+7; its lane L therefore carries
   // chunk (L&7) of the row of lane (L&56)+t.  The per-lane source addresses depend only on the cells, so they are
-  // built ONCE per density call (two ds_bpermute per instruction) and serve all 4*nspec units: the unit is
-  // selected by the 12-bit immediate offset (k*128, +512 to reach into the next species).
-  __device__ __forceinline__ void stage_prepare(int cell, unsigned long long (&a)[8]) const {
-    const int lane = threadIdx.x;
-    const unsigned long long base =
-        reinterpret_cast<unsigned long long>(coef) + (unsigned long long)(unsigned)cell * (unsigned long long)(nspec * 512);
+  // built ONCE per density call (two ds_bpermute per instruction) and serve all 4*nspec units: the plane is
+  // selected by the 12-bit immediate offset (k*128), the species by moving a[] by +-512 B.
+  __device__ __forceinline__ void stage_prepare(int cell, unsigned long long (&a)[8], int species = 0) const {
+    int lane = threadIdx.x;
+    asm volatile("" : "+v"(lane)); // (see res_addr)
+    const unsigned long long base = reinterpret_cast<unsigned long long>(coef) +
+                                    (unsigned long long)(unsigned)cell * (unsigned long long)(nspec * 512) + (unsigned)(species * 512);
     const int blo = (int)(unsigned)base, bhi = (int)(unsigned)(base >> 32);
     const int p = lane & 7, g = lane & 56;
 #pragma unroll
@@ -472,7 +486,8 @@ struct InterpModel {
   }
   // LDS byte addresses of this lane's 8 logical chunks inside ring buffer 0
   __device__ __forceinline__ static void read_addrs(double *lds, unsigned (&ra)[8]) {
-    const int lane = threadIdx.x;
+    int lane = threadIdx.x;
+    asm volatile("" : "+v"(lane)); // recomputed per call, not held across the caller's loops (see res_addr)
     const unsigned base = (unsigned)(unsigned long long)((SRT_AS3 char *)lds) + TILE_PAD_BYTES +
                           (unsigned)((8 * (lane & 7) + (lane >> 3)) * 128);
 #pragma unroll
@@ -483,11 +498,55 @@ struct InterpModel {
   // resident in L2, made the kernel 9 % slower -- default policy everywhere.)
   template <int IMM, int J, int AUX = 0>
   __device__ __forceinline__ static void issue_unit(const unsigned long long (&a)[8], double *lds) {
+    static_assert(IMM <= MAX_UNIT_IMM, "the DMA base would reach into the residency header");
     SRT_AS3 char *ring = (SRT_AS3 char *)lds + TILE_PAD_BYTES;
 #pragma unroll
     for (int t = 0; t < 8; ++t)
       __builtin_amdgcn_global_load_lds((const SRT_AS1 void *)a[t], (SRT_AS3 void *)(ring + (J * UNIT_BYTES + t * 1024 - IMM)),
                                        16, IMM, AUX);
+  }
+  // Re-stage the four planes of one species (buffers 0..3, k = 3..0) for the lanes flagged in `miss` only.  Instruction t
+  // writes the row slots of lanes (j & 56) + t, so it runs for the 8-lane groups whose owner lane of t is flagged; an
+  // instruction whose exec is empty is skipped, so the caller cannot count these loads: it waits for all of them.
+  __device__ __forceinline__ static void restage_species(const unsigned long long (&a)[8], double *lds, unsigned long long miss) {
+    SRT_AS3 char *ring = (SRT_AS3 char *)lds + TILE_PAD_BYTES;
+    const unsigned owners = (unsigned)(miss >> (threadIdx.x & 56)) & 0xffu; // bit t: the owner of instruction t in this group
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      if ((owners >> t) & 1u) {
+        const SRT_AS1 void *src = (const SRT_AS1 void *)a[t];
+        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (0 * UNIT_BYTES + t * 1024 - 384)), 16, 384, 0);
+        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (1 * UNIT_BYTES + t * 1024 - 256)), 16, 256, 0);
+        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (2 * UNIT_BYTES + t * 1024 - 128)), 16, 128, 0);
+        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (3 * UNIT_BYTES + t * 1024)), 16, 0, 0);
+      }
+    }
+    wait_vm<0>();
+  }
+  // The residency header (RES_*), read and written by inline asm: like read_unit, out of sight of the compiler's wait-count
+  // pass, which would otherwise make these LDS accesses wait for DMA of earlier lookups that has long landed.
+  // (The lane index goes through an empty asm so that the address is recomputed at each use rather than hoisted out of
+  // the caller's loops and held in a register: the trace kernel has none to spare.)
+  __device__ __forceinline__ static unsigned res_addr(double *lds) {
+    int lane = threadIdx.x;
+    asm volatile("" : "+v"(lane));
+    return (unsigned)(unsigned long long)((SRT_AS3 char *)lds) + (unsigned)(RES_CELL_BYTES + 4 * lane);
+  }
+  __device__ __forceinline__ static void ring_read(double *lds, int &state, int &held) {
+    asm volatile("ds_read_b32 %0, %2 offset:%3\n\t"
+                 "ds_read_b32 %1, %2\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(state), "=&v"(held)
+                 : "v"(res_addr(lds)), "n"(RES_STATE_BYTES - RES_CELL_BYTES)
+                 : "memory");
+    state = __builtin_amdgcn_readfirstlane(state);
+  }
+  // called by all 64 lanes
+  __device__ __forceinline__ static void ring_write_state(double *lds, int state) {
+    asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(res_addr(lds)), "v"(state), "n"(RES_STATE_BYTES - RES_CELL_BYTES) : "memory");
+  }
+  __device__ __forceinline__ static void ring_write_cell(double *lds, int cell) {
+    asm volatile("ds_write_b32 %0, %1" ::"v"(res_addr(lds)), "v"(cell) : "memory");
   }
   template <int N>
   __device__ __forceinline__ static void wait_vm() {
@@ -569,9 +628,15 @@ struct InterpModel {
   // Densities at the evalrhs stencil around c (offsets d) and, when NE == 1, at one more point `extra`.
   // Ns[0] centre, Ns[1+2a] = c + d_a e_a, Ns[2+2a] = c - d_a e_a, Ns[7] = extra.
   //
-  // The 4*nspec units of the call stream through the ring with a lookahead of three: while the lane evaluates
-  // plane k of species s from buffer (3-k), the DMA of the next three units is in flight (the loads of one wave
-  // retire in issue order, so s_waitcnt vmcnt(24) = "all but the youngest three units have landed").
+  //
+  // Residency: the ring holds one species of every lane's block, and a lookup ends with the four planes of its last
+  // species in buffers 0..3 -- exactly where the next lookup's first species goes.  So lookups alternate the species
+  // order (0 .. nspec-1, then back down; each species is evaluated on its own, so the order changes no bit), and one
+  // starts from what the ring holds: lanes whose cell is the one their rows were staged for (RES_CELL) use them as they
+  // are, the others' rows are re-staged (restage_species, exec-masked).  Then the units stream through the ring with a
+  // lookahead of four: each buffer, once read, takes the same plane of the next species (the loads of one wave retire
+  // in issue order, so s_waitcnt vmcnt(24) = "all but the youngest three units have landed").  Nothing is in flight
+  // when the call returns.
   template <int NE>
   __device__ __forceinline__ void density_stencil(const double c[3], const double d[3], const double *extra,
                                                   double (&Ns)[7 + NE][4], double *lds, bool = true) const {
@@ -585,13 +650,26 @@ struct InterpModel {
     if (NE) {
       extra_same = (ax.locate(extra[0], E[0]) == ci) && (ay.locate(extra[1], E[1]) == cj) && (az.locate(extra[2], E[2]) == ck);
     }
+    const int cell = cell_id(ci, cj, ck);
+    int state, held;
+    ring_read(lds, state, held);
+    const bool desc = state == RING_HOLDS_LAST;                                  // wave-uniform: start where the ring is
+    const unsigned long long miss = __ballot(state == RING_INVALID || held != cell); // wave-uniform
+#ifdef SRT_TRIP_TIMING
+    if (threadIdx.x == 0) srt_tt_lds()[14] += (unsigned long long)__popcll(miss), srt_tt_lds()[15] += miss ? 1ull : 0ull;
+#endif
+    // recorded now (nothing reads the header before the next lookup): what the ring will hold when this one returns --
+    // this cell's rows, and its last species, after which the next lookup goes through the species the other way round
+    ring_write_cell(lds, cell);
+    ring_write_state(lds, desc ? RING_HOLDS_FIRST : RING_HOLDS_LAST);
     unsigned long long a[8];
     unsigned ra[8];
-    stage_prepare(cell_id(ci, cj, ck), a);
+    stage_prepare(cell, a, desc ? nspec - 1 : 0);
     read_addrs(lds, ra);
-    issue_unit<384, 0>(a, lds); // species 0: planes 3, 2, 1 -> buffers 0, 1, 2
-    issue_unit<256, 1>(a, lds);
-    issue_unit<128, 2>(a, lds);
+    const unsigned long long step = desc ? (unsigned long long)-512ll : 512ull;
+    if (miss) restage_species(a, lds, miss); // (waits for its loads)
+#pragma unroll
+    for (int t = 0; t < 8; ++t) a[t] += step; // from here on a[] addresses the species after the one being evaluated
     double acc[7 + NE][4];
 #pragma unroll
     for (int i = 0; i < 7 + NE; ++i)
@@ -599,41 +677,46 @@ struct InterpModel {
       for (int k = 0; k < 4; ++k) acc[i][k] = 0.0;
 #pragma unroll 1
     for (int s = 0; s < nspec; ++s) {
-      const bool last = s + 1 >= nspec; // wave-uniform
+      const bool more = s + 1 < nspec; // wave-uniform
+      const int sp = desc ? nspec - 1 - s : s; // the species in the ring
       double vz[7 + NE];
 #pragma unroll
       for (int i = 0; i < 7 + NE; ++i) vz[i] = 0.0;
       d2_t cf[8];
-      issue_unit<0, 3>(a, lds); // plane 0 of this species
+      // Four units in flight while another species follows, else those of this species still to be read.  (The first
+      // species' units are resident or re-staged: fewer loads than that are in flight, the waits pass at once.)  A buffer
+      // takes the next species' plane once the plane it holds has been evaluated.
       wait_vm<24>();
       read_unit<0>(ra, cf);
       plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 3
-      if (!last) {
-        issue_unit<512 + 384, 0>(a, lds); // plane 3 of the next species
+      if (more) {
+        issue_unit<384, 0>(a, lds);
         wait_vm<24>();
       } else wait_vm<16>();
       read_unit<1>(ra, cf);
       plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 2
-      if (!last) {
-        issue_unit<512 + 256, 1>(a, lds);
+      if (more) {
+        issue_unit<256, 1>(a, lds);
         wait_vm<24>();
       } else wait_vm<8>();
       read_unit<2>(ra, cf);
       plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 1
-      if (!last) {
-        issue_unit<512 + 128, 2>(a, lds);
+      if (more) {
+        issue_unit<128, 2>(a, lds);
         wait_vm<24>();
       } else wait_vm<0>();
       read_unit<3>(ra, cf);
       plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 0
-      // s is a run-time loop index: select statically so that acc stays in registers (no scratch)
+      if (more) issue_unit<0, 3>(a, lds);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) a[t] += step;
+      // sp is a run-time value: select statically so that acc stays in registers (no scratch)
 #pragma unroll
       for (int i = 0; i < 7 + NE; ++i)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc[i][k] = (k == s) ? vz[i] : acc[i][k];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) a[t] += 512;
+        for (int k = 0; k < 4; ++k) acc[i][k] = (k == sp) ? vz[i] : acc[i][k];
     }
+    wait_vm<0>(); // (already true) nothing may stay in flight into the caller's row stores, refills or exit
     // rare: a stencil point (offsets ~1e-6 |x| against cells of ~1e5..1e6 m) or the free point lies in another cell
     if (__any(!same || !extra_same)) {
       if (!same) {
@@ -679,6 +762,7 @@ struct InterpModel {
     }
     unsigned long long a[8];
     unsigned ra[8];
+    ring_write_state(lds, RING_INVALID); // the ring's rows are overwritten below without being recorded
     stage_prepare(cell_id(ci, cj, ck), a);
     read_addrs(lds, ra);
     double acc[NP][4];
@@ -728,5 +812,8 @@ struct InterpModel {
       for (int s = 0; s < 4; ++s) Ns[i][s] = (s < nspec) ? exp(acc[i][s]) : 0.0; // Ns = exp(Ns) (:206)
   }
 };
+// The ring's residency state starts invalid in every kernel; a lane given a new ray has its rows re-staged.
+__device__ __forceinline__ void tile_reset(const InterpModel &, double *lds) { InterpModel::ring_write_state(lds, RING_INVALID); }
+__device__ __forceinline__ void new_ray_hook(const InterpModel &, double *lds, bool) { InterpModel::ring_write_cell(lds, -1); }
 
 } // namespace srt
