@@ -1088,8 +1088,11 @@ struct ScatteredModel {
       n8[gg] = two & 0xFFFF, n8[gg + 1] = (int)((unsigned)two >> 16);
     }
     if (lane < 8) o->hin8[rev3] = hmine;
-    // (smallest distance = 1 / the largest reciprocal; lanes without a sample hold 1e300; the wave maximum is wave-uniform)
-    const double rmin_w = fdiv(1.0, wave_max_nonneg(fdiv(1.0, rmin_l)));
+    // (smallest distance = 1 / the largest reciprocal; lanes without a sample hold 1e300; the wave maximum is wave-uniform.
+    // A sample AT the centre has rmin_l = 0, whose fdiv reciprocal is NaN (rcp gives inf, its Newton step -0 * inf), and the
+    // maximum drops NaN lanes: the clamp to 1e-300 makes it win instead, rmin = 1e-300 then fails the tier's distance test,
+    // and the stencil takes the series with that sample's weight evaluated directly)
+    const double rmin_w = fdiv(1.0, wave_max_nonneg(fdiv(1.0, fmax(rmin_l, 1.0e-300))));
     if (lane == 0) {
 #pragma unroll
       for (int gg = 0; gg < 8; ++gg) o->cnt8[gg] = n8[gg];

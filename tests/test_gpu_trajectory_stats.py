@@ -7,7 +7,7 @@ Adaptive step sequences are chaotic at rounding level (SURVEY A-9: the reference
 shifted by 1e-9 relative (~1 cm) -- measured in the same test, on the same rays:
   * per-ray distance between the position curves (cubic-Hermite resampled on a common time grid),
   * agreement of stop codes, of the first controller decisions (time stamps of rows 1-3) and of the row totals;
-and, on 10 k rays of each BASELINE workload (1 k for the scattered one: its oracle does 4e3 steps/s), the distributions:
+and, on 10 k rays of each BASELINE workload (6 k for the scattered one: its oracle does 2.4e3 steps/s), the distributions:
 stop-code histogram, distribution of the final radial distance (Kolmogorov-Smirnov distance; ray-by-ray closeness), total
 accepted steps.
 """
@@ -164,12 +164,9 @@ def distribution_check(tag, g, o, pos, d, w, kw, outputper):
     assert np.all(np.abs(hg - ho) <= 3 * sigma + 3 * np.abs(hp - ho) + 2e-3), msg
     assert abs(steps - osteps) <= max(0.02 * osteps, 3 * abs(psteps - osteps)), msg
     assert ks_g <= 3 * ks_p + 3.0 / np.sqrt(n), msg
-    # (shares of n rays: three binomial sigma of the oracle's own share, as for the histogram -- 0.02 at 10 k rays is 4 sigma, at the
-    # scattered model's 1 000 rays it was 1.3 sigma: a build that beat the oracle's self-comparison on every other line failed it
-    # by one ray, 0.401 against 0.422 - 0.02)
-    sig = lambda q: 3.0 * np.sqrt(max(q * (1.0 - q), 1e-4) / n)
-    assert close_g >= close_p - max(0.02, sig(close_p)), msg
-    assert np.mean(stop == ostop) >= np.mean(pstop == ostop) - max(0.02, sig(np.mean(pstop == ostop))), msg
+    # (shares of n rays: 0.02 is three binomial sigma of a share near 0.4 at 6 000 rays, four at 10 000)
+    assert close_g >= close_p - 0.02, msg
+    assert np.mean(stop == ostop) >= np.mean(pstop == ostop) - 0.02, msg
 
 
 def ks_distance(a, b):
@@ -205,7 +202,7 @@ def test_distribution_config2_interp():
 
 def test_distribution_config4_scattered(tmp_path):
     """BASELINE config[4] (scattered model, maxsteps 64, outputper 8) on a 60 k-sample set of the same plasmasphere over
-    the same cube (the oracle's kd-tree set-up for 825 k samples alone takes minutes), first 1 000 rays of its launch set."""
+    the same cube (the oracle's kd-tree set-up for 825 k samples alone takes minutes), first 6 000 rays of its launch set."""
     from oracle import oracle
     from stanford_raytracer_amd import api
 
@@ -215,6 +212,6 @@ def test_distribution_config4_scattered(tmp_path):
     g = api.Model.scattered_file(pf, window_scale=1.5, order=2, exact=0, local_window_scale=5.0)
     o = oracle.Model.scattered_file(pf, window_scale=1.5, order=2, exact=0, local_window_scale=5.0, perm_seed=2 | 0x80000000)
     pos, d, w = wl.launch_set(1_000_000, 5)
-    pos, d, w = pos[:1000], d[:1000], w[:1000]
+    pos, d, w = pos[:6000], d[:6000], w[:6000]
     kw = dict(fixedstep=0, dt0=1e-3, dtmax=0.1, maxerr=5e-4, tmax=0.5, maxsteps=64, del_=1e-6, minalt=wl.MINALT)
     distribution_check("config[4] scattered", g, o, pos, d, w, kw, 8)
