@@ -1504,11 +1504,11 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   HIP_OK(hipEventRecord(sl.done, st));
 #ifdef SRT_TRIP_TIMING
   if (getenv("SRT_TRIP_TIMING")) {
-    unsigned long long h[16];
+    unsigned long long h[srt::TT_SLOTS];
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpyFromSymbol(h, HIP_SYMBOL(srt_trip_cycles), sizeof h));
     fprintf(stderr, "srt trip cycles:");
-    for (int i = 0; i < 16; ++i) fprintf(stderr, " %llu", h[i]);
+    for (int i = 0; i < srt::TT_SLOTS; ++i) fprintf(stderr, " %llu", h[i]);
     fprintf(stderr, "\n");
     memset(h, 0, sizeof h);
     HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(srt_trip_cycles), h, sizeof h));

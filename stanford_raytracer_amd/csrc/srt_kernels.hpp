@@ -14,7 +14,10 @@ namespace srt {
 // launch when the environment variable SRT_TRIP_TIMING is set): 0 stencil densities inside the stages, 1 rest of evalrhs,
 // 2 end-point stencil densities, 3 error term, 4 root re-projection, 5 end-point right-hand side, 6 bookkeeping, 7 trips,
 // 8 trips with <= 8 active lanes, 9 loop top (stop tests, refill), 10 stage bookkeeping; interp model (counts, not cycles):
-// 14 lane-lookups whose rows were not resident in the ring, 15 wave-lookups that re-staged any rows.
+// 14 lane-lookups whose rows were not resident in the ring, 15 wave-lookups that re-staged any rows; cycles of a lookup
+// (InterpModel::density_stencil): 16 from its start to the first DMA instruction, 17 issuing the masked re-stage, 18 the cell
+// searches of the offset points and the free point, 19 waiting for the re-stage, 20 the species loop, 21 from the last wait to
+// the return, 22 wave-lookups.
 #ifdef SRT_TRIP_TIMING
 #define SRT_TT_BEGIN() __builtin_amdgcn_sched_barrier(0); unsigned long long tt0_ = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0)
 #define SRT_TT(slot)                                                                                   \
@@ -377,7 +380,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
   const unsigned long long srt_wave_t0 = __builtin_readcyclecounter();
 #endif
 #ifdef SRT_TRIP_TIMING
-  if (threadIdx.x < 16) srt_tt_lds()[threadIdx.x] = 0ull;
+  if (threadIdx.x < TT_SLOTS) srt_tt_lds()[threadIdx.x] = 0ull;
   __syncthreads();
 #endif
   SRT_TT_BEGIN();
@@ -662,7 +665,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
   }
 #ifdef SRT_TRIP_TIMING
   __syncthreads();
-  if (threadIdx.x < 16) atomicAdd(&srt_trip_cycles[threadIdx.x], srt_tt_lds()[threadIdx.x]);
+  if (threadIdx.x < TT_SLOTS) atomicAdd(&srt_trip_cycles[threadIdx.x], srt_tt_lds()[threadIdx.x]);
 #endif
 #ifdef SRT_PHASE_TIMING
   if (lane == 0) {

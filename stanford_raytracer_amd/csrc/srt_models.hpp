@@ -30,13 +30,19 @@ enum RingState : int { RING_INVALID = 0, RING_HOLDS_FIRST = 1, RING_HOLDS_LAST =
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 #ifdef SRT_TRIP_TIMING
-__device__ unsigned long long srt_trip_cycles[16]; // see srt_kernels.hpp
+constexpr int TT_SLOTS = 24;
+__device__ unsigned long long srt_trip_cycles[TT_SLOTS]; // see srt_kernels.hpp
 // per-wave sums live in LDS and are flushed once at the end of the kernel: a global atomic per mark would itself show up in
-// whatever waits on memory next (every wave adding to the same 16 words)
+// whatever waits on memory next (every wave adding to the same words)
 __device__ __forceinline__ unsigned long long *srt_tt_lds() {
-  __shared__ unsigned long long acc[16];
+  __shared__ unsigned long long acc[TT_SLOTS];
   return acc;
 }
+// A time stamp of the interp lookup.  Kept in scalar registers and added to the LDS sums only when the lookup has nothing in
+// flight any more: an LDS access the compiler can see waits for all LDS-DMA issued before it.
+#define SRT_LK_MARK(var_) __builtin_amdgcn_sched_barrier(0); const unsigned long long var_ = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0)
+#else
+#define SRT_LK_MARK(var_) do {} while (0)
 #endif
 
 #ifdef SRT_PHASE_TIMING
@@ -442,8 +448,11 @@ struct InterpModel {
     for (int i = 0; i < NP; ++i) out[i] = vz[i];
   }
 
-  // rare path: one point, straight from global memory (lane-divergent)
-  __device__ __noinline__ void point_direct(double x, double y, double z, double lnN[4]) const {
+  // rare path: one point, straight from global memory (lane-divergent).  Out of line, in two forms: ln N_s of the species the
+  // model has (the others' entries are left alone), or the densities themselves, exp of that and 0.0 for the others -- the
+  // stencil lookup calls the latter once per straddling point and must not carry an inlined exp for each.
+  template <bool EXP>
+  __device__ __forceinline__ void point_direct_body(double x, double y, double z, double out[4]) const {
     double xl, yl, zl;
     int ci = ax.locate(x, xl), cj = ay.locate(y, yl), ck = az.locate(z, zl);
     const double *base = coef + (size_t)cell_id(ci, cj, ck) * (size_t)(nspec * 64);
@@ -453,10 +462,12 @@ struct InterpModel {
         const double2 *a = reinterpret_cast<const double2 *>(base + s * 64);
         double x1[1] = {xl}, y1[1] = {yl}, z1[1] = {zl}, o1[1];
         eval<1>([&](int q) { return a[q]; }, x1, y1, z1, o1);
-        lnN[s] = o1[0];
-      }
+        out[s] = EXP ? exp(o1[0]) : o1[0]; // Ns = exp(Ns) (:206)
+      } else if (EXP) out[s] = 0.0;
     }
   }
+  __device__ __noinline__ void point_direct(double x, double y, double z, double lnN[4]) const { point_direct_body<false>(x, y, z, lnN); }
+  __device__ __noinline__ void point_direct_exp(double x, double y, double z, double N[4]) const { point_direct_body<true>(x, y, z, N); }
 
   // ------------------------------------------------------------------------------------------
   // Staging of coefficient blocks through the LDS ring.
@@ -507,8 +518,9 @@ struct InterpModel {
   }
   // Re-stage the four planes of one species (buffers 0..3, k = 3..0) for the lanes flagged in `miss` only.  Instruction t
   // writes the row slots of lanes (j & 56) + t, so it runs for the 8-lane groups whose owner lane of t is flagged; an
-  // instruction whose exec is empty is skipped, so the caller cannot count these loads: it waits for all of them.
-  __device__ __forceinline__ static void restage_species(const unsigned long long (&a)[8], double *lds, unsigned long long miss) {
+  // instruction whose exec is empty is skipped, so the caller cannot count these loads: it waits for all of them
+  // (wait_vm<0>, whenever it likes: nothing here waits).
+  __device__ __forceinline__ static void restage_issue(const unsigned long long (&a)[8], double *lds, unsigned long long miss) {
     SRT_AS3 char *ring = (SRT_AS3 char *)lds + TILE_PAD_BYTES;
     const unsigned owners = (unsigned)(miss >> (threadIdx.x & 56)) & 0xffu; // bit t: the owner of instruction t in this group
 #pragma unroll
@@ -521,7 +533,6 @@ struct InterpModel {
         __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (3 * UNIT_BYTES + t * 1024)), 16, 0, 0);
       }
     }
-    wait_vm<0>();
   }
   // The residency header (RES_*), read and written by inline asm: like read_unit, out of sight of the compiler's wait-count
   // pass, which would otherwise make these LDS accesses wait for DMA of earlier lookups that has long landed.
@@ -637,19 +648,18 @@ struct InterpModel {
   // lookahead of four: each buffer, once read, takes the same plane of the next species (the loads of one wave retire
   // in issue order, so s_waitcnt vmcnt(24) = "all but the youngest three units have landed").  Nothing is in flight
   // when the call returns.
+  //
+  // One wave per SIMD: only the wave's own instructions hide its waits.  So what needs no staged data runs where loads are
+  // in flight: the cell searches of the offset points and of the free point behind the re-stage's DMA instructions, and the
+  // exp of a species (Ns = exp(Ns), :206) behind the issue of the next species' units.  Only the last species' exp is exposed.
   template <int NE>
   __device__ __forceinline__ void density_stencil(const double c[3], const double d[3], const double *extra,
                                                   double (&Ns)[7 + NE][4], double *lds, bool = true) const {
+    SRT_LK_MARK(lk0_);
+    // Only the centre's cell decides what is staged: its three searches come first, those of the offset points and of the
+    // free point wait until the re-stage is in flight (below).
     double X[3], Y[3], Z[3], E[3] = {0.0, 0.0, 0.0};
     const int ci = ax.locate(c[0], X[0]), cj = ay.locate(c[1], Y[0]), ck = az.locate(c[2], Z[0]);
-    bool same = true;
-    same = same && (ax.locate(c[0] + d[0], X[1]) == ci) && (ax.locate(c[0] - d[0], X[2]) == ci);
-    same = same && (ay.locate(c[1] + d[1], Y[1]) == cj) && (ay.locate(c[1] - d[1], Y[2]) == cj);
-    same = same && (az.locate(c[2] + d[2], Z[1]) == ck) && (az.locate(c[2] - d[2], Z[2]) == ck);
-    bool extra_same = true;
-    if (NE) {
-      extra_same = (ax.locate(extra[0], E[0]) == ci) && (ay.locate(extra[1], E[1]) == cj) && (az.locate(extra[2], E[2]) == ck);
-    }
     const int cell = cell_id(ci, cj, ck);
     int state, held;
     ring_read(lds, state, held);
@@ -667,7 +677,29 @@ struct InterpModel {
     stage_prepare(cell, a, desc ? nspec - 1 : 0);
     read_addrs(lds, ra);
     const unsigned long long step = desc ? (unsigned long long)-512ll : 512ull;
-    if (miss) restage_species(a, lds, miss); // (waits for its loads)
+    SRT_LK_MARK(lk1_);
+    if (miss) restage_issue(a, lds, miss);
+    SRT_LK_MARK(lk2_);
+    // While the re-staged rows travel: the cell searches of the six offset points and of the free point (plane_stencil and
+    // the straddle test after the loop need them, the staging does not).  Pure arithmetic may move across an asm statement,
+    // so the offsets pass through an empty one: what depends on them cannot be computed above the DMA instructions.
+    double dd[3] = {d[0], d[1], d[2]}, ee[3] = {NE ? extra[0] : 0.0, NE ? extra[1] : 0.0, NE ? extra[2] : 0.0};
+#pragma unroll
+    for (int a_ = 0; a_ < 3; ++a_) {
+      asm volatile("" : "+v"(dd[a_]));
+      if (NE) asm volatile("" : "+v"(ee[a_]));
+    }
+    bool same = true;
+    same = same && (ax.locate(c[0] + dd[0], X[1]) == ci) && (ax.locate(c[0] - dd[0], X[2]) == ci);
+    same = same && (ay.locate(c[1] + dd[1], Y[1]) == cj) && (ay.locate(c[1] - dd[1], Y[2]) == cj);
+    same = same && (az.locate(c[2] + dd[2], Z[1]) == ck) && (az.locate(c[2] - dd[2], Z[2]) == ck);
+    bool extra_same = true;
+    if (NE) {
+      extra_same = (ax.locate(ee[0], E[0]) == ci) && (ay.locate(ee[1], E[1]) == cj) && (az.locate(ee[2], E[2]) == ck);
+    }
+    SRT_LK_MARK(lk3_);
+    wait_vm<0>(); // the re-staged rows (exec-masked instructions cannot be counted: all of them)
+    SRT_LK_MARK(lk4_);
 #pragma unroll
     for (int t = 0; t < 8; ++t) a[t] += step; // from here on a[] addresses the species after the one being evaluated
     double acc[7 + NE][4];
@@ -710,12 +742,16 @@ struct InterpModel {
       if (more) issue_unit<0, 3>(a, lds);
 #pragma unroll
       for (int t = 0; t < 8; ++t) a[t] += step;
+      // Ns = exp(Ns) (:206), species by species: all but the last one's run while the next species' four units are in flight.
       // sp is a run-time value: select statically so that acc stays in registers (no scratch)
 #pragma unroll
-      for (int i = 0; i < 7 + NE; ++i)
+      for (int i = 0; i < 7 + NE; ++i) {
+        const double e = exp(vz[i]);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc[i][k] = (k == sp) ? vz[i] : acc[i][k];
+        for (int k = 0; k < 4; ++k) acc[i][k] = (k == sp) ? e : acc[i][k];
+      }
     }
+    SRT_LK_MARK(lk5_);
     wait_vm<0>(); // (already true) nothing may stay in flight into the caller's row stores, refills or exit
     // rare: a stencil point (offsets ~1e-6 |x| against cells of ~1e5..1e6 m) or the free point lies in another cell
     if (__any(!same || !extra_same)) {
@@ -724,16 +760,16 @@ struct InterpModel {
         for (int ax_ = 0; ax_ < 3; ++ax_)
 #pragma unroll
           for (int sg = 0; sg < 2; ++sg) {
-            double pt[3] = {c[0], c[1], c[2]}, t[4] = {0.0, 0.0, 0.0, 0.0};
+            double pt[3] = {c[0], c[1], c[2]}, t[4];
             pt[ax_] = sg ? c[ax_] - d[ax_] : c[ax_] + d[ax_];
-            point_direct(pt[0], pt[1], pt[2], t);
+            point_direct_exp(pt[0], pt[1], pt[2], t);
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[1 + 2 * ax_ + sg][k] = t[k];
           }
       }
       if (NE && !extra_same) {
-        double t[4] = {0.0, 0.0, 0.0, 0.0};
-        point_direct(extra[0], extra[1], extra[2], t);
+        double t[4];
+        point_direct_exp(extra[0], extra[1], extra[2], t);
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[7 + NE - 1][k] = t[k];
       }
@@ -741,7 +777,15 @@ struct InterpModel {
 #pragma unroll
     for (int i = 0; i < 7 + NE; ++i)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) Ns[i][k] = (k < nspec) ? exp(acc[i][k]) : 0.0; // Ns = exp(Ns) (:206)
+      for (int k = 0; k < 4; ++k) Ns[i][k] = acc[i][k]; // (species the model does not have: never selected, 0.0)
+#ifdef SRT_TRIP_TIMING
+    SRT_LK_MARK(lk6_);
+    if (threadIdx.x == 0) {
+      unsigned long long *tt_ = srt_tt_lds();
+      tt_[16] += lk1_ - lk0_, tt_[17] += lk2_ - lk1_, tt_[18] += lk3_ - lk2_, tt_[19] += lk4_ - lk3_, tt_[20] += lk5_ - lk4_;
+      tt_[21] += lk6_ - lk5_, tt_[22] += 1ull;
+    }
+#endif
   }
 
   // NP unrelated points (layered kernels; not performance-critical): same units, no lookahead.
