@@ -12,13 +12,19 @@ constexpr double FM_PI = 3.14159265358979323846;
 // steps on the reciprocal, quotient, one residual correction -- without the v_div_scale / v_div_fmas /
 // v_div_fixup wrapper that only matters for operands or quotients near the ends of the exponent range, so the
 // result is bit-identical to a/b wherever that wrapper would not have scaled (8 instructions instead of 11).
-__device__ __forceinline__ double fdiv(double a, double b) {
+// The sequence in two halves, so that divisions by the same b share the first: fdiv_recip(b) is the refined reciprocal (it
+// depends on b alone), fdiv_r(a, b, r) the quotient and its correction.  fdiv(a, b) == fdiv_r(a, b, fdiv_recip(b)) bit for bit.
+__device__ __forceinline__ double fdiv_recip(double b) {
   double r = __builtin_amdgcn_rcp(b);
   r = fma(fma(-b, r, 1.0), r, r);
   r = fma(fma(-b, r, 1.0), r, r);
+  return r;
+}
+__device__ __forceinline__ double fdiv_r(double a, double b, double r) {
   double q = a * r;
   return fma(fma(-b, q, a), r, q);
 }
+__device__ __forceinline__ double fdiv(double a, double b) { return fdiv_r(a, b, fdiv_recip(b)); }
 
 // Elementary functions on the argument ranges of the scattered model's per-sample passes (srt_scattered.hpp) and of the
 // T04_s field (srt_t04.hpp): each is the textbook (fdlibm) kernel without the library's range handling -- arguments there

@@ -17,7 +17,10 @@ namespace srt {
 // 14 lane-lookups whose rows were not resident in the ring, 15 wave-lookups that re-staged any rows; cycles of a lookup
 // (InterpModel::density_stencil): 16 from its start to the first DMA instruction, 17 issuing the masked re-stage, 18 the cell
 // searches of the offset points and the free point, 19 waiting for the re-stage, 20 the species loop, 21 from the last wait to
-// the return, 22 wave-lookups.
+// the return, 22 wave-lookups; inside the species loop (part of 20): 24 the waits for the LDS reads of the 16 units, 25 the
+// waits for the units' DMA.  (A time stamp is itself counted in lgkmcnt: taking one waits for the LDS reads in flight, so
+// with reads issued a unit ahead slot 24 is a lower bound and the marks of 24 / 25 lengthen the loop: judge the schedule by
+// slot 20 and by the release build.)
 #ifdef SRT_TRIP_TIMING
 #define SRT_TT_BEGIN() __builtin_amdgcn_sched_barrier(0); unsigned long long tt0_ = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0)
 #define SRT_TT(slot)                                                                                   \

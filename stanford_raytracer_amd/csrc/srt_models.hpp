@@ -30,7 +30,7 @@ enum RingState : int { RING_INVALID = 0, RING_HOLDS_FIRST = 1, RING_HOLDS_LAST =
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 #ifdef SRT_TRIP_TIMING
-constexpr int TT_SLOTS = 24;
+constexpr int TT_SLOTS = 26;
 __device__ unsigned long long srt_trip_cycles[TT_SLOTS]; // see srt_kernels.hpp
 // per-wave sums live in LDS and are flushed once at the end of the kernel: a global atomic per mark would itself show up in
 // whatever waits on memory next (every wave adding to the same words)
@@ -41,8 +41,16 @@ __device__ __forceinline__ unsigned long long *srt_tt_lds() {
 // A time stamp of the interp lookup.  Kept in scalar registers and added to the LDS sums only when the lookup has nothing in
 // flight any more: an LDS access the compiler can see waits for all LDS-DMA issued before it.
 #define SRT_LK_MARK(var_) __builtin_amdgcn_sched_barrier(0); const unsigned long long var_ = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0)
+// Sums of many short spans inside a lookup (the LDS reads of the 16 units, the waits for their DMA), also in scalar registers:
+// SRT_LK_SPAN_BEGIN() ... SRT_LK_SPAN_END(sum_) adds the cycles between the two to sum_.
+#define SRT_LK_SUMS() unsigned long long lkrd_ = 0ull, lkvm_ = 0ull, lks0_ = 0ull
+#define SRT_LK_SPAN_BEGIN() do { __builtin_amdgcn_sched_barrier(0); lks0_ = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define SRT_LK_SPAN_END(sum_) do { __builtin_amdgcn_sched_barrier(0); sum_ += __builtin_readcyclecounter() - lks0_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define SRT_LK_MARK(var_) do {} while (0)
+#define SRT_LK_SUMS() do {} while (0)
+#define SRT_LK_SPAN_BEGIN() do {} while (0)
+#define SRT_LK_SPAN_END(sum_) do {} while (0)
 #endif
 
 #ifdef SRT_PHASE_TIMING
@@ -395,16 +403,39 @@ struct Axis {
   // maxloc(.., mask = 0 <= (xi - x)) (libtricubic.f95:835-840): number of nodes <= xi, and the local
   // coordinate (:842-856)
   __device__ __forceinline__ int locate(double xi, double &xl) const {
-    double f = (xi - min) * rdel;
-    int g;
-    if (!(f >= 0.0)) g = 0;
-    else if (f >= (double)n) g = n;
-    else g = (int)f + 1;
+    double lo;
+    return locate(xi, xl, fdiv_recip(del), lo);
+  }
+  // The same search with the refined reciprocal of del handed in (r = fdiv_recip(del): a caller with several searches on this
+  // axis computes it once) and node(g - 1) handed back (lo; not meaningful for g = 0).  Written with selects only, on a copy
+  // of the axis the caller holds in registers: nothing in it depends on the outcome of another search, so the searches of a
+  // lookup can issue back to back.
+  __device__ __forceinline__ int locate(double xi, double &xl, double r, double &lo) const {
+    const double f = (xi - min) * rdel;
+    // the guess: 0 below the grid (and for a NaN), n above it, else trunc(f) + 1 -- converted from the clamped value, so that
+    // the conversion is defined for every f and can be computed unconditionally
+    const double fc = fmin(fmax(f, 0.0), (double)n);
+    int g = (int)fc + 1;
+    g = (f >= (double)n) ? n : g;
+    g = !(f >= 0.0) ? 0 : g;
     // the quotient is within one node of the exact answer: one correction each way, no loops
-    g += (g < n && node(g) <= xi) ? 1 : 0;
-    g -= (g > 0 && node(g - 1) > xi) ? 1 : 0;
-    xl = (g >= 1 && g < n) ? fdiv(xi - node(g - 1), del) : 0.0;
+    g += (int)((g < n) & (node(g) <= xi));
+    g -= (int)((g > 0) & (node(g - 1) > xi));
+    lo = node(g - 1);
+    xl = ((g >= 1) & (g < n)) ? fdiv_r(xi - lo, del, r) : 0.0;
     return g;
+  }
+  // Does xi lie in cell g of this axis, that is locate(xi, .) == g, and if so its local coordinate: what a lookup needs of a
+  // point near one whose cell it has searched already.  lo = node(g - 1) (as locate hands it back), hi = node(g), r =
+  // fdiv_recip(del).  The two comparisons equal the search's outcome for every xi, NaN and the infinities included (a NaN
+  // is in cell 0 like in locate, hence !(hi <= xi) and not xi < hi), and for offsets of any size: locate returns the true
+  // count of nodes <= xi (tests/test_cell_from_centre.py).  xl is locate's own expression on the same operands; it is only
+  // meaningful when the answer is true.
+  __device__ __forceinline__ bool in_cell(double xi, int g, double lo, double hi, double r, double &xl) const {
+    const bool below_hi = (g < n) ? !(hi <= xi) : true;
+    const bool above_lo = (g > 0) ? (xi >= lo) : true;
+    xl = ((g >= 1) & (g < n)) ? fdiv_r(xi - lo, del, r) : 0.0;
+    return below_hi & above_lo;
   }
 };
 
@@ -413,9 +444,9 @@ struct InterpModel {
   Axis ax, ay, az;
   int nspec;
 
-  __device__ __forceinline__ int cell_id(int ci, int cj, int ck) const {
-    return (ck * (ay.n + 1) + cj) * (ax.n + 1) + ci;
-  }
+  // cell = (ck*(ny+1)+cj)*(nx+1)+ci (the one definition: the lookup calls the static form on its register copies of the axes)
+  __device__ __forceinline__ static int cell_id(int nx, int ny, int ci, int cj, int ck) { return (ck * (ny + 1) + cj) * (nx + 1) + ci; }
+  __device__ __forceinline__ int cell_id(int ci, int cj, int ck) const { return cell_id(ax.n, ay.n, ci, cj, ck); }
 
   // tricubic_eval with derx=dery=derz=0 (libtricubic.f95:658-695) for NP points that share one cell:
   // nested Horner, coefficient-outer / point-inner so each coefficient is read once.
@@ -559,6 +590,13 @@ struct InterpModel {
   __device__ __forceinline__ static void ring_write_cell(double *lds, int cell) {
     asm volatile("ds_write_b32 %0, %1" ::"v"(res_addr(lds)), "v"(cell) : "memory");
   }
+  // a value that is the same in every lane, moved to scalar registers
+  __device__ __forceinline__ static double uniform(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+  }
   template <int N>
   __device__ __forceinline__ static void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -579,6 +617,39 @@ struct InterpModel {
                  : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3]), "=&v"(c[4]), "=&v"(c[5]), "=&v"(c[6]), "=&v"(c[7])
                  : "v"(ra[0]), "v"(ra[1]), "v"(ra[2]), "v"(ra[3]), "v"(ra[4]), "v"(ra[5]), "v"(ra[6]), "v"(ra[7]),
                    "n"(J * UNIT_BYTES)
+                 : "memory");
+  }
+
+  // The same eight reads without the wait (c[6], c[7] first: the order plane_stencil consumes them in); wait_lgkm releases
+  // them.  LDS reads return in order, so with another unit's reads issued behind these, wait_lgkm<8> means "these eight have
+  // landed".  (Anything else counted in lgkmcnt between these reads and that wait only makes it wait longer; the lookup holds
+  // what it needs in registers, so nothing is.)
+  // Between this statement and that wait the compiler takes the eight destinations for written: nothing in the source keeps it
+  // from copying, spilling or moving one to an accumulator register there, which would save stale data.  It does not today,
+  // in any kernel that inlines the lookup, the spilling T04_s variants included: tools/check_read_ahead_isa.py checks the
+  // compiled ISA for it and has to be run again after a change of compiler, of flags or of the lookup's register pressure.
+  template <int J>
+  __device__ __forceinline__ static void read_unit_issue(const unsigned (&ra)[8], d2_t (&c)[8]) {
+    asm volatile("ds_read_b128 %6, %14 offset:%16\n\t"
+                 "ds_read_b128 %7, %15 offset:%16\n\t"
+                 "ds_read_b128 %4, %12 offset:%16\n\t"
+                 "ds_read_b128 %5, %13 offset:%16\n\t"
+                 "ds_read_b128 %2, %10 offset:%16\n\t"
+                 "ds_read_b128 %3, %11 offset:%16\n\t"
+                 "ds_read_b128 %0, %8 offset:%16\n\t"
+                 "ds_read_b128 %1, %9 offset:%16"
+                 : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3]), "=&v"(c[4]), "=&v"(c[5]), "=&v"(c[6]), "=&v"(c[7])
+                 : "v"(ra[0]), "v"(ra[1]), "v"(ra[2]), "v"(ra[3]), "v"(ra[4]), "v"(ra[5]), "v"(ra[6]), "v"(ra[7]),
+                   "n"(J * UNIT_BYTES)
+                 : "memory");
+  }
+  // Wait until at most N of the reads issued after those of unit c are outstanding.  The unit passes through the statement,
+  // so nothing that uses it is scheduled above the wait (register-only arithmetic is otherwise moved across an asm wait).
+  template <int N>
+  __device__ __forceinline__ static void wait_lgkm(d2_t (&c)[8]) {
+    asm volatile("s_waitcnt lgkmcnt(%8)"
+                 : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7])
+                 : "n"(N)
                  : "memory");
   }
 
@@ -647,20 +718,27 @@ struct InterpModel {
   // are, the others' rows are re-staged (restage_species, exec-masked).  Then the units stream through the ring with a
   // lookahead of four: each buffer, once read, takes the same plane of the next species (the loads of one wave retire
   // in issue order, so s_waitcnt vmcnt(24) = "all but the youngest three units have landed").  Nothing is in flight
-  // when the call returns.
+  // when the call returns.  From LDS a unit goes to one of two register sets, read while the plane before it is being
+  // evaluated from the other.
   //
   // One wave per SIMD: only the wave's own instructions hide its waits.  So what needs no staged data runs where loads are
   // in flight: the cell searches of the offset points and of the free point behind the re-stage's DMA instructions, and the
   // exp of a species (Ns = exp(Ns), :206) behind the issue of the next species' units.  Only the last species' exp is exposed.
+  // The same goes for the LDS reads: a unit's eight reads are issued before the plane in front of it is evaluated, not after.
   template <int NE>
   __device__ __forceinline__ void density_stencil(const double c[3], const double d[3], const double *extra,
                                                   double (&Ns)[7 + NE][4], double *lds, bool = true) const {
     SRT_LK_MARK(lk0_);
     // Only the centre's cell decides what is staged: its three searches come first, those of the offset points and of the
     // free point wait until the re-stage is in flight (below).
+    // The axes are read once, into registers (the asm statements below clobber memory: a field read through the model after
+    // one of them is loaded again), and each axis' divisions share one refined reciprocal of its spacing (wave-uniform).
     double X[3], Y[3], Z[3], E[3] = {0.0, 0.0, 0.0};
-    const int ci = ax.locate(c[0], X[0]), cj = ay.locate(c[1], Y[0]), ck = az.locate(c[2], Z[0]);
-    const int cell = cell_id(ci, cj, ck);
+    const Axis lx = ax, ly = ay, lz = az;
+    const double rx = uniform(fdiv_recip(lx.del)), ry = uniform(fdiv_recip(ly.del)), rz = uniform(fdiv_recip(lz.del));
+    double xlo, ylo, zlo; // node(cell - 1) per axis
+    const int ci = lx.locate(c[0], X[0], rx, xlo), cj = ly.locate(c[1], Y[0], ry, ylo), ck = lz.locate(c[2], Z[0], rz, zlo);
+    const int cell = cell_id(lx.n, ly.n, ci, cj, ck);
     int state, held;
     ring_read(lds, state, held);
     const bool desc = state == RING_HOLDS_LAST;                                  // wave-uniform: start where the ring is
@@ -689,14 +767,24 @@ struct InterpModel {
       asm volatile("" : "+v"(dd[a_]));
       if (NE) asm volatile("" : "+v"(ee[a_]));
     }
-    bool same = true;
-    same = same && (ax.locate(c[0] + dd[0], X[1]) == ci) && (ax.locate(c[0] - dd[0], X[2]) == ci);
-    same = same && (ay.locate(c[1] + dd[1], Y[1]) == cj) && (ay.locate(c[1] - dd[1], Y[2]) == cj);
-    same = same && (az.locate(c[2] + dd[2], Z[1]) == ck) && (az.locate(c[2] - dd[2], Z[2]) == ck);
+    // Of these points only two things are needed: whether they lie in the centre's cell (if not, the straddle path below
+    // searches for itself) and their local coordinate there -- two comparisons against the cell's own nodes and one division
+    // by the shared reciprocal each (Axis::in_cell), all independent of each other.
+    const double xhi = lx.node(ci), yhi = ly.node(cj), zhi = lz.node(ck);
+    const bool same = lx.in_cell(c[0] + dd[0], ci, xlo, xhi, rx, X[1]) & lx.in_cell(c[0] - dd[0], ci, xlo, xhi, rx, X[2]) &
+                      ly.in_cell(c[1] + dd[1], cj, ylo, yhi, ry, Y[1]) & ly.in_cell(c[1] - dd[1], cj, ylo, yhi, ry, Y[2]) &
+                      lz.in_cell(c[2] + dd[2], ck, zlo, zhi, rz, Z[1]) & lz.in_cell(c[2] - dd[2], ck, zlo, zhi, rz, Z[2]);
     bool extra_same = true;
     if (NE) {
-      extra_same = (ax.locate(ee[0], E[0]) == ci) && (ay.locate(ee[1], E[1]) == cj) && (az.locate(ee[2], E[2]) == ck);
+      extra_same = lx.in_cell(ee[0], ci, xlo, xhi, rx, E[0]) & ly.in_cell(ee[1], cj, ylo, yhi, ry, E[1]) &
+                   lz.in_cell(ee[2], ck, zlo, zhi, rz, E[2]);
     }
+    // ... and what they produce cannot be computed below the wait either (without branches in it, all of this is pure
+    // arithmetic that would otherwise sink to its first use: the coordinates into the species loop, the two answers, kept
+    // as one word per lane, to the straddle test behind it)
+    unsigned away = (same ? 0u : 1u) | (extra_same ? 0u : 2u);
+    asm volatile("" : "+v"(away), "+v"(X[1]), "+v"(X[2]), "+v"(Y[1]), "+v"(Y[2]), "+v"(Z[1]), "+v"(Z[2]));
+    if (NE) asm volatile("" : "+v"(E[0]), "+v"(E[1]), "+v"(E[2]));
     SRT_LK_MARK(lk3_);
     wait_vm<0>(); // the re-staged rows (exec-masked instructions cannot be counted: all of them)
     SRT_LK_MARK(lk4_);
@@ -707,6 +795,7 @@ struct InterpModel {
     for (int i = 0; i < 7 + NE; ++i)
 #pragma unroll
       for (int k = 0; k < 4; ++k) acc[i][k] = 0.0;
+    SRT_LK_SUMS();
 #pragma unroll 1
     for (int s = 0; s < nspec; ++s) {
       const bool more = s + 1 < nspec; // wave-uniform
@@ -716,30 +805,42 @@ struct InterpModel {
       for (int i = 0; i < 7 + NE; ++i) vz[i] = 0.0;
       d2_t cf[8];
       // Four units in flight while another species follows, else those of this species still to be read.  (The first
-      // species' units are resident or re-staged: fewer loads than that are in flight, the waits pass at once.)  A buffer
-      // takes the next species' plane once the plane it holds has been evaluated.
-      wait_vm<24>();
-      read_unit<0>(ra, cf);
+      // species' units are resident or re-staged: fewer loads than that are in flight, the waits pass at once.)
+      // Two register sets: the reads of unit k + 1 are issued before unit k's are waited for (lgkmcnt(8) releases the older
+      // eight), so a unit's LDS round trip runs under the plane before it; the plane's results pass through an empty asm,
+      // which keeps its arithmetic in front of the next unit's reads.  A buffer takes the next species' plane once its
+      // own reads have returned -- after unit k + 1's reads have been issued, so at that point the loads that may still be
+      // in flight are one unit fewer than the ring holds: vmcnt(16), or what is left of the last species.
+#define SRT_LOOP_WAIT_VM(n_) do { SRT_LK_SPAN_BEGIN(); wait_vm<n_>(); SRT_LK_SPAN_END(lkvm_); } while (0)
+#define SRT_LOOP_PIN_VZ() do { asm volatile("" : "+v"(vz[0]), "+v"(vz[1]), "+v"(vz[2]), "+v"(vz[3]), "+v"(vz[4]), "+v"(vz[5]), "+v"(vz[6])); if (NE) asm volatile("" : "+v"(vz[7 + NE - 1])); } while (0)
+      d2_t cg[8];
+      SRT_LOOP_WAIT_VM(24);
+      read_unit_issue<0>(ra, cf);
+      SRT_LOOP_WAIT_VM(16);
+      read_unit_issue<1>(ra, cg);
+      SRT_LK_SPAN_BEGIN(); wait_lgkm<8>(cf); SRT_LK_SPAN_END(lkrd_);
+      if (more) issue_unit<384, 0>(a, lds);
       plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 3
-      if (more) {
-        issue_unit<384, 0>(a, lds);
-        wait_vm<24>();
-      } else wait_vm<16>();
-      read_unit<1>(ra, cf);
-      plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 2
-      if (more) {
-        issue_unit<256, 1>(a, lds);
-        wait_vm<24>();
-      } else wait_vm<8>();
-      read_unit<2>(ra, cf);
+      SRT_LOOP_PIN_VZ();
+      if (more) SRT_LOOP_WAIT_VM(16);
+      else SRT_LOOP_WAIT_VM(8);
+      read_unit_issue<2>(ra, cf);
+      SRT_LK_SPAN_BEGIN(); wait_lgkm<8>(cg); SRT_LK_SPAN_END(lkrd_);
+      if (more) issue_unit<256, 1>(a, lds);
+      plane_stencil<NE>(cg, X, Y, Z, E, vz); // k = 2
+      SRT_LOOP_PIN_VZ();
+      if (more) SRT_LOOP_WAIT_VM(16);
+      else SRT_LOOP_WAIT_VM(0);
+      read_unit_issue<3>(ra, cg);
+      SRT_LK_SPAN_BEGIN(); wait_lgkm<8>(cf); SRT_LK_SPAN_END(lkrd_);
+      if (more) issue_unit<128, 2>(a, lds);
       plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 1
-      if (more) {
-        issue_unit<128, 2>(a, lds);
-        wait_vm<24>();
-      } else wait_vm<0>();
-      read_unit<3>(ra, cf);
-      plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 0
+      SRT_LOOP_PIN_VZ();
+      SRT_LK_SPAN_BEGIN(); wait_lgkm<0>(cg); SRT_LK_SPAN_END(lkrd_);
       if (more) issue_unit<0, 3>(a, lds);
+      plane_stencil<NE>(cg, X, Y, Z, E, vz); // k = 0
+#undef SRT_LOOP_WAIT_VM
+#undef SRT_LOOP_PIN_VZ
 #pragma unroll
       for (int t = 0; t < 8; ++t) a[t] += step;
       // Ns = exp(Ns) (:206), species by species: all but the last one's run while the next species' four units are in flight.
@@ -754,8 +855,8 @@ struct InterpModel {
     SRT_LK_MARK(lk5_);
     wait_vm<0>(); // (already true) nothing may stay in flight into the caller's row stores, refills or exit
     // rare: a stencil point (offsets ~1e-6 |x| against cells of ~1e5..1e6 m) or the free point lies in another cell
-    if (__any(!same || !extra_same)) {
-      if (!same) {
+    if (__any(away != 0u)) {
+      if (away & 1u) {
 #pragma unroll
         for (int ax_ = 0; ax_ < 3; ++ax_)
 #pragma unroll
@@ -767,7 +868,7 @@ struct InterpModel {
             for (int k = 0; k < 4; ++k) acc[1 + 2 * ax_ + sg][k] = t[k];
           }
       }
-      if (NE && !extra_same) {
+      if (NE && (away & 2u)) {
         double t[4];
         point_direct_exp(extra[0], extra[1], extra[2], t);
 #pragma unroll
@@ -784,6 +885,7 @@ struct InterpModel {
       unsigned long long *tt_ = srt_tt_lds();
       tt_[16] += lk1_ - lk0_, tt_[17] += lk2_ - lk1_, tt_[18] += lk3_ - lk2_, tt_[19] += lk4_ - lk3_, tt_[20] += lk5_ - lk4_;
       tt_[21] += lk6_ - lk5_, tt_[22] += 1ull;
+      tt_[24] += lkrd_, tt_[25] += lkvm_;
     }
 #endif
   }
