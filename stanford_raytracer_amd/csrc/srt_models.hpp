@@ -26,6 +26,13 @@ constexpr int RES_STATE_BYTES = WAVE * 4;
 constexpr int RES_END_BYTES = RES_STATE_BYTES + WAVE * 4;
 constexpr int MAX_UNIT_IMM = 384; // largest immediate of an LDS-DMA load (plane 3 of a species)
 static_assert(RES_END_BYTES <= TILE_PAD_BYTES - MAX_UNIT_IMM, "the header must lie below every biased DMA base");
+// One M0 per half unit: piece t of a unit (one DMA instruction, 1 KiB) has the destination base of piece t & 4 and reaches its own
+// KiB through its immediate, which therefore carries piece_step(t) on top of the plane's offset; stage_prepare moves a[t] down by
+// the same amount, so that a piece reads and writes the bytes it would with a base of its own (tests/
+// test_ring_piece_immediates_layout.py).  The immediate field of a global load takes -4096 ... 4095 on gfx950; only 0 ... 4095
+// is used: what a negative immediate does to the LDS address has not been probed.
+constexpr int piece_step(int t) { return (t & 3) * 1024; }
+static_assert(MAX_UNIT_IMM + piece_step(3) <= 4095 && piece_step(0) == 0, "every piece immediate must lie within 0 ... 4095");
 enum RingState : int { RING_INVALID = 0, RING_HOLDS_FIRST = 1, RING_HOLDS_LAST = 2 };
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -510,7 +517,8 @@ struct InterpModel {
   // Filled by LDS-DMA: instruction t of a unit writes 1 KiB = row slots 8t..8t+7; its lane L therefore carries
   // chunk (L&7) of the row of lane (L&56)+t.  The per-lane source addresses depend only on the cells, so they are
   // built ONCE per density call (two ds_bpermute per instruction) and serve all 4*nspec units: the plane is
-  // selected by the 12-bit immediate offset (k*128), the species by moving a[] by +-512 B.
+  // selected by the immediate offset (k*128, plus piece_step(t): a[t] is biased by -piece_step(t) to make up for it, so a[t]
+  // alone may point up to 3 KiB in front of the lane's block), the species by moving a[] by +-512 B.
   __device__ __forceinline__ void stage_prepare(int cell, unsigned long long (&a)[8], int species = 0) const {
     int lane = threadIdx.x;
     asm volatile("" : "+v"(lane)); // (see res_addr)
@@ -523,7 +531,8 @@ struct InterpModel {
       const int src = (g + t) << 2;
       const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(src, blo);
       const unsigned hi = (unsigned)__builtin_amdgcn_ds_bpermute(src, bhi);
-      a[t] = (((unsigned long long)hi << 32) | (unsigned long long)lo) + (unsigned long long)(((p - t) & 7) << 4);
+      a[t] = (((unsigned long long)hi << 32) | (unsigned long long)lo) +
+             (unsigned long long)(long long)((((p - t) & 7) << 4) - piece_step(t));
     }
   }
   // LDS byte addresses of this lane's 8 logical chunks inside ring buffer 0
@@ -535,35 +544,39 @@ struct InterpModel {
 #pragma unroll
     for (int q = 0; q < 8; ++q) ra[q] = base + (unsigned)(((q + lane) & 7) << 4);
   }
-  // DMA of one unit into ring buffer J; IMM = byte offset of the unit relative to the addresses in a[]
+  // DMA of one unit into ring buffer J; IMM = byte offset of the unit's plane inside a species' block.  Eight explicit pieces
+  // with compile-time bases and immediates: pieces 0-3 and 4-7 share a base, so the compiler writes M0 (and the s_nop that must
+  // follow a write of it) twice per unit, not eight times.  The lowest base is still ring - MAX_UNIT_IMM.
   // AUX = cache policy bits of the load.  (Measured: nt on the species >= 1 units, hoping to keep species 0
   // resident in L2, made the kernel 9 % slower -- default policy everywhere.)
   template <int IMM, int J, int AUX = 0>
   __device__ __forceinline__ static void issue_unit(const unsigned long long (&a)[8], double *lds) {
     static_assert(IMM <= MAX_UNIT_IMM, "the DMA base would reach into the residency header");
     SRT_AS3 char *ring = (SRT_AS3 char *)lds + TILE_PAD_BYTES;
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-      __builtin_amdgcn_global_load_lds((const SRT_AS1 void *)a[t], (SRT_AS3 void *)(ring + (J * UNIT_BYTES + t * 1024 - IMM)),
-                                       16, IMM, AUX);
+#define SRT_PIECE(t_)                                                                                                          \
+  __builtin_amdgcn_global_load_lds((const SRT_AS1 void *)a[t_],                                                                \
+                                   (SRT_AS3 void *)(ring + (J * UNIT_BYTES + (t_) * 1024 - piece_step(t_) - IMM)), 16,         \
+                                   IMM + piece_step(t_), AUX)
+    SRT_PIECE(0); SRT_PIECE(1); SRT_PIECE(2); SRT_PIECE(3); SRT_PIECE(4); SRT_PIECE(5); SRT_PIECE(6); SRT_PIECE(7);
+#undef SRT_PIECE
   }
   // Re-stage the four planes of one species (buffers 0..3, k = 3..0) for the lanes flagged in `miss` only.  Instruction t
   // writes the row slots of lanes (j & 56) + t, so it runs for the 8-lane groups whose owner lane of t is flagged; an
   // instruction whose exec is empty is skipped, so the caller cannot count these loads: it waits for all of them
-  // (wait_vm<0>, whenever it likes: nothing here waits).
+  // (wait_vm<0>, whenever it likes: nothing here waits).  The four pieces under one t go to four different buffers (8 KiB
+  // apart, more than an immediate spans), and the pieces of different t sit under different branches: the re-stage keeps an M0
+  // per piece; only its immediates carry piece_step(t), because a[t] is biased.
   __device__ __forceinline__ static void restage_issue(const unsigned long long (&a)[8], double *lds, unsigned long long miss) {
     SRT_AS3 char *ring = (SRT_AS3 char *)lds + TILE_PAD_BYTES;
     const unsigned owners = (unsigned)(miss >> (threadIdx.x & 56)) & 0xffu; // bit t: the owner of instruction t in this group
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      if ((owners >> t) & 1u) {
-        const SRT_AS1 void *src = (const SRT_AS1 void *)a[t];
-        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (0 * UNIT_BYTES + t * 1024 - 384)), 16, 384, 0);
-        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (1 * UNIT_BYTES + t * 1024 - 256)), 16, 256, 0);
-        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (2 * UNIT_BYTES + t * 1024 - 128)), 16, 128, 0);
-        __builtin_amdgcn_global_load_lds(src, (SRT_AS3 void *)(ring + (3 * UNIT_BYTES + t * 1024)), 16, 0, 0);
-      }
-    }
+#define SRT_RS(t_, j_)                                                                                                         \
+  __builtin_amdgcn_global_load_lds((const SRT_AS1 void *)a[t_],                                                                \
+                                   (SRT_AS3 void *)(ring + ((j_) * UNIT_BYTES + (t_) * 1024 - piece_step(t_) - (3 - (j_)) * 128)), \
+                                   16, (3 - (j_)) * 128 + piece_step(t_), 0)
+#define SRT_RS4(t_) if ((owners >> (t_)) & 1u) { SRT_RS(t_, 0); SRT_RS(t_, 1); SRT_RS(t_, 2); SRT_RS(t_, 3); }
+    SRT_RS4(0) SRT_RS4(1) SRT_RS4(2) SRT_RS4(3) SRT_RS4(4) SRT_RS4(5) SRT_RS4(6) SRT_RS4(7)
+#undef SRT_RS4
+#undef SRT_RS
   }
   // The residency header (RES_*), read and written by inline asm: like read_unit, out of sight of the compiler's wait-count
   // pass, which would otherwise make these LDS accesses wait for DMA of earlier lookups that has long landed.
@@ -656,8 +669,13 @@ struct InterpModel {
   // One k-plane of tricubic_eval (libtricubic.f95:658-695, derx=dery=derz=0) for the 7-point stencil of evalrhs
   // (centre, x+-, y+-, z+-) plus NE (0/1) free points, all in one cell.  c[2j], c[2j+1] = a(0..3 + 4j + 16k).
   // Points that share a coordinate share the partial Horner sums; per point the operations and their order are
-  // exactly those of a plain nested Horner evaluation (k outer, j middle, i inner).
-  template <int NE>
+  // exactly those of a plain nested Horner evaluation (k outer, j middle, i inner) -- less the first step of each sum: a plain
+  // Horner sum starts at 0.0, so its first step is fma(0.0, y, v), and that is assigned here (j = 3 in every plane; FIRST: the
+  // k = 3 plane assigns vz).  No bit of Ns changes: the local coordinates y are finite and >= +0 (locate and in_cell return
+  // 0.0 or a quotient of finite operands with xi >= lo), so fma(+0.0, y, v) == v for every v but -0.0, which it turns into
+  // +0.0; a zero of either sign is absorbed by the next non-zero term, and if every later term is zero as well the sum ends in
+  // exp, where exp(+-0) = 1 (tests/test_gpu_horner_first_terms.py).  27 of 343 FMAs per species, 32 of 424 with the free point.
+  template <int NE, bool FIRST = false>
   __device__ __forceinline__ static void plane_stencil(const d2_t (&c)[8], const double (&X)[3], const double (&Y)[3],
                                                        const double (&Z)[3], const double (&E)[3],
                                                        double (&vz)[7 + NE]) {
@@ -668,15 +686,23 @@ struct InterpModel {
       double h0 = fma(fma(fma(hi.y, X[0], hi.x), X[0], lo.y), X[0], lo.x);
       double hp = fma(fma(fma(hi.y, X[1], hi.x), X[1], lo.y), X[1], lo.x);
       double hm = fma(fma(fma(hi.y, X[2], hi.x), X[2], lo.y), X[2], lo.x);
-      vc = fma(vc, Y[0], h0);
-      vxp = fma(vxp, Y[0], hp);
-      vxm = fma(vxm, Y[0], hm);
-      vyp = fma(vyp, Y[1], h0);
-      vym = fma(vym, Y[2], h0);
-      if (NE) {
-        double he = fma(fma(fma(hi.y, E[0], hi.x), E[0], lo.y), E[0], lo.x);
-        ve = fma(ve, E[1], he);
+      double he = 0.0;
+      if (NE) he = fma(fma(fma(hi.y, E[0], hi.x), E[0], lo.y), E[0], lo.x);
+      if (j == 3) {
+        vc = h0, vxp = hp, vxm = hm, vyp = h0, vym = h0, ve = he;
+      } else {
+        vc = fma(vc, Y[0], h0);
+        vxp = fma(vxp, Y[0], hp);
+        vxm = fma(vxm, Y[0], hm);
+        vyp = fma(vyp, Y[1], h0);
+        vym = fma(vym, Y[2], h0);
+        if (NE) ve = fma(ve, E[1], he);
       }
+    }
+    if (FIRST) {
+      vz[0] = vc, vz[1] = vxp, vz[2] = vxm, vz[3] = vyp, vz[4] = vym, vz[5] = vc, vz[6] = vc;
+      if (NE) vz[7 + NE - 1] = ve;
+      return;
     }
     vz[0] = fma(vz[0], Z[0], vc);
     vz[1] = fma(vz[1], Z[0], vxp);
@@ -799,7 +825,6 @@ struct InterpModel {
 #pragma unroll 1
     for (int s = 0; s < nspec; ++s) {
       const bool more = s + 1 < nspec; // wave-uniform
-      const int sp = desc ? nspec - 1 - s : s; // the species in the ring
       double vz[7 + NE];
 #pragma unroll
       for (int i = 0; i < 7 + NE; ++i) vz[i] = 0.0;
@@ -820,7 +845,7 @@ struct InterpModel {
       read_unit_issue<1>(ra, cg);
       SRT_LK_SPAN_BEGIN(); wait_lgkm<8>(cf); SRT_LK_SPAN_END(lkrd_);
       if (more) issue_unit<384, 0>(a, lds);
-      plane_stencil<NE>(cf, X, Y, Z, E, vz); // k = 3
+      plane_stencil<NE, true>(cf, X, Y, Z, E, vz); // k = 3
       SRT_LOOP_PIN_VZ();
       if (more) SRT_LOOP_WAIT_VM(16);
       else SRT_LOOP_WAIT_VM(8);
@@ -844,12 +869,23 @@ struct InterpModel {
 #pragma unroll
       for (int t = 0; t < 8; ++t) a[t] += step;
       // Ns = exp(Ns) (:206), species by species: all but the last one's run while the next species' four units are in flight.
-      // sp is a run-time value: select statically so that acc stays in registers (no scratch)
+      // The loop is rolled and sp a run-time value, so acc cannot be indexed by it (scratch), and selecting the entry costs
+      // eight v_cndmask per point.  Instead each species is put in front and the others move up one place: in the
+      // descending order every species ends in its own place; the ascending order ends reversed and is turned round once
+      // behind the loop (wave-uniform).  Places beyond nspec keep the 0.0 they start with.
 #pragma unroll
       for (int i = 0; i < 7 + NE; ++i) {
         const double e = exp(vz[i]);
+        acc[i][3] = acc[i][2], acc[i][2] = acc[i][1], acc[i][1] = acc[i][0], acc[i][0] = e;
+      }
+    }
+    if (!desc) { // wave-uniform
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc[i][k] = (k == sp) ? e : acc[i][k];
+      for (int i = 0; i < 7 + NE; ++i) {
+        double t0 = acc[i][0], t1 = acc[i][1], t2 = acc[i][2], t3 = acc[i][3];
+        if (nspec == 4) acc[i][0] = t3, acc[i][1] = t2, acc[i][2] = t1, acc[i][3] = t0;
+        else if (nspec == 3) acc[i][0] = t2, acc[i][2] = t0;
+        else if (nspec == 2) acc[i][0] = t1, acc[i][1] = t0;
       }
     }
     SRT_LK_MARK(lk5_);
