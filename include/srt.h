@@ -7,15 +7,15 @@
  *                        raytracer_stopconditions)            (signature fortran/raytracer.f95:609-642)
  * becomes one batched call, srt_trace_batch().  The reference's plugin callback
  *     subroutine funcPlasmaParams(x, qs, Ns, ms, nus, B0, funcPlasmaParamsData)   (raytracer.f95:121-129)
- * cannot be a host callback on a GPU path; its three in-scope implementations are selected by the
- * model handle instead (modelnum 1 / 3 / 4 of raytracer_driver.f95:256-770) and are exposed for
+ * cannot be a host callback on a GPU path; its four in-scope implementations are selected by the
+ * model handle instead (modelnum 1 / 3 / 4 / 6 of raytracer_driver.f95:256-992) and are exposed for
  * point queries through srt_plasma_params().
  *
  * Conventions: plain pointers and sizes, no C++ or torch types.  All arrays are HOST memory unless a
  * function name ends in _device.  Vectors are AoS: pos0[i*3+c].  Every function returns 0 on success
  * or a negative SRT_E* code; srt_last_error() gives the text.  Per-ray failures never abort a batch:
  * they are reported through stopcond (same codes as raytracer.f95:324-353, plus SRT_STOP_NUMERIC for
- * the reference's process-killing `stop` on an SVD failure, blas.f95:208-211).
+ * the reference's process-killing `stop` on an SVD failure, blas.f95:208-211, or in modelnum 6's check_crossing).
  * The library needs a gfx950 GPU; there is no CPU fallback.
  */
 #ifndef SRT_H
@@ -116,6 +116,19 @@ int srt_model_create_scattered_file(const char *ptsfile, int yearday, int msec, 
 int srt_model_create_scattered_file_root(const char *ptsfile, int yearday, int msec, double window_scale,
                                          int order, int exact, double local_window_scale, int64_t root_sample,
                                          srt_model **out);
+/* modelnum=6: simple_3d_model_adapter.f95; fixed_MLT = 1 holds every point at MLT hours.
+ * The closed-form "simplified GCPM": Carpenter-Anderson plasmasphere, Kp- and MLT-dependent plasmapause (pp_profile_d.f95),
+ * MLT-dependent trough, a fitted ionosphere merged at an altitude the model searches for, He+ / O+ / H+ fractions; no
+ * tables.  kp = the driver's --kp, yearday / msec = itime (day of year for the plasmasphere's annual term, dipole tilt).
+ * DEFINED BEHAVIOUR where the adapter reads three locals that nothing sets (the reference's toolchain zeroes them with
+ * -finit-local-zero); all three are 0 at every call:
+ *   rz12 in ne_ps (:106, shadows the module parameter): the sunspot term of x234 is 0.00127*0 - 0.0635;
+ *   diff in find_intersection_iono_ps (:585): the first trip of the altitude search never flips its step, 2000 -> 3000 km;
+ *   switch_cap in funcPlasmaParams (:790): aHeH is not reduced.
+ * With do_cap = 0 the polar-cap code (ne_cap, poleward_edge) is dead and is not part of this library.  Where the
+ * reference stops the process ("Failed to find knee in check_crossing") the densities are NaN and a traced ray ends with
+ * SRT_STOP_NUMERIC. */
+int srt_model_create_simple3d(double kp, int fixed_MLT, double MLT, int yearday, int msec, srt_model **out);
 /* The step before the path: sample a model's funcPlasmaParams on a regular nx x ny x nz grid in
  * log space ON THE DEVICE -- gcpm_dens_model_buildgrid.f95:160-300 with any model handle in place of GCPM.
  * compder = 1 adds the seven explicit finite-difference blocks (d = 1e-3*|pos|, :197-296); compder = 0 leaves the
@@ -162,7 +175,7 @@ int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenko, const ch
 /* parmod[10] = Pdyn (nPa), Dst (nT), ByIMF, BzIMF (nT), W1 .. W6: the driver's --tsyganenko_* flags */
 int srt_model_set_tsyganenko_params(srt_model *m, const double parmod[10]);
 void srt_model_destroy(srt_model *m);
-int srt_model_kind(const srt_model *m);  /* 1, 3 or 4 */
+int srt_model_kind(const srt_model *m);  /* 1, 3, 4 or 6 */
 int srt_model_nspec(const srt_model *m);
 int srt_model_species(const srt_model *m, double qs[SRT_MAXSPEC], double ms[SRT_MAXSPEC]);
 int64_t srt_model_device_bytes(const srt_model *m);

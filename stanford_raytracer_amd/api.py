@@ -81,6 +81,7 @@ def lib():
                                                   C.c_double, C.POINTER(vp)]
     L.srt_model_create_scattered_file_root.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                                        C.c_double, C.c_int64, C.POINTER(vp)]
+    L.srt_model_create_simple3d.argtypes = [C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
     L.srt_model_set_field.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
     L.srt_model_set_tsyganenko_params.argtypes = [vp, dp]
     L.srt_model_destroy.argtypes = [vp]
@@ -209,6 +210,16 @@ class Model:
         h = C.c_void_p()
         _check(lib().srt_model_create_scattered_file_root(os.fsencode(ptsfile), yearday, msec, window_scale, order,
                                                           exact, local_window_scale, int(root_sample), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def simple3d(cls, kp, yearday=2010001, msec=0, fixed_mlt=None):
+        """modelnum 6, the closed-form simplified GCPM (simple_3d_model_adapter.f95).  fixed_mlt: None = MLT from each point's
+        longitude; a number = every point is held at that many hours MLT (the driver's --fixed_MLT=1 --MLT=...)."""
+        h = C.c_void_p()
+        fixed = 0 if fixed_mlt is None else 1
+        _check(lib().srt_model_create_simple3d(float(kp), fixed, 0.0 if fixed_mlt is None else float(fixed_mlt), yearday,
+                                               msec, C.byref(h)))
         return cls(h)
 
     def build_grid(self, nx, ny, nz, bounds, compder=False):

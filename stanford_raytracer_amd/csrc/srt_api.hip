@@ -15,6 +15,7 @@
 #include "srt_host.hpp"
 #include "srt_kernels.hpp"
 #include "srt_scattered.hpp"
+#include "srt_simple3d.hpp"
 #include "srt_sampler.hpp"
 #include "srt_damping.hpp"
 #include <hipcub/hipcub.hpp>
@@ -136,6 +137,7 @@ struct srt_model {
   NgoModel ngo{};
   InterpModel interp{};
   ScatteredModel scat{};
+  Simple3dModel s3{};
   double *d_pts = nullptr;
   double *d_xyz = nullptr; // scattered model: the sample positions once more, SoA [3][npts] (the candidate scans read only these)
   int *d_cells = nullptr;
@@ -238,6 +240,9 @@ static int model_finish(srt_model *m) {
   } else if (m->kind == 4) {
     HIP_OK(hipMalloc(&m->d_model, sizeof(ScatteredModel)));
     HIP_OK(hipMemcpy(m->d_model, &m->scat, sizeof(ScatteredModel), hipMemcpyHostToDevice));
+  } else if (m->kind == 6) {
+    HIP_OK(hipMalloc(&m->d_model, sizeof(Simple3dModel)));
+    HIP_OK(hipMemcpy(m->d_model, &m->s3, sizeof(Simple3dModel), hipMemcpyHostToDevice));
   }
   hipDeviceProp_t p;
   m->device = current_device();
@@ -434,6 +439,36 @@ extern "C" int srt_model_create_ngo(const char *configfile, int yearday, int mse
     return srt_set_error(SRT_EDEVICE, "ngo normalisation kernel failed: %s", hipGetErrorString(e));
   }
   g.ane0 = g.ane0 * cfg.dsdens / ani1;
+  const double e_ = 1.602e-19;
+  double qs[4] = {e_ * -1.0, e_, e_, e_};
+  double ms[4] = {9.10938188e-31, 1.6726e-27, 4.0 * 1.6726e-27, 16.0 * 1.6726e-27};
+  fill_common(m->cm, 4, qs, ms, yearday, msec);
+  rc = model_finish(m);
+  if (rc) {
+    srt_model_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return SRT_OK;
+}
+
+// ---- simple3d: closed form, nothing but a handful of constants (srt_simple3d.hpp) -------------------
+extern "C" int srt_model_create_simple3d(double kp, int fixed_MLT, double MLT, int yearday, int msec, srt_model **out) {
+  if (!out) return srt_set_error(SRT_EINVAL, "null argument");
+  if (fixed_MLT != 0 && fixed_MLT != 1) return srt_set_error(SRT_EINVAL, "fixed_MLT must be 0 or 1");
+  if (!std::isfinite(kp) || (fixed_MLT == 1 && !std::isfinite(MLT))) return srt_set_error(SRT_EINVAL, "kp and MLT must be finite");
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  srt_model *m = new srt_model;
+  m->kind = 6;
+  m->nspec = 4;
+  m->s3.c.kp = kp;
+  m->s3.c.year = yearday / 1000; // iyear = itime(1)/1000, doy = itime(1) - iyear*1000 (:743-744)
+  m->s3.c.doy = yearday - m->s3.c.year * 1000;
+  m->s3.c.fixed_mlt = fixed_MLT;
+  m->s3.c.mlt = MLT;
+  // the adapter's own species constants (:813-815)
   const double e_ = 1.602e-19;
   double qs[4] = {e_ * -1.0, e_, e_, e_};
   double ms[4] = {9.10938188e-31, 1.6726e-27, 4.0 * 1.6726e-27, 16.0 * 1.6726e-27};
@@ -757,6 +792,8 @@ static int sample_model_on_grid(srt_model *src, int compder, int nx, int ny, int
     hipLaunchKernelGGL((sample_grid_kernel<NgoModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const NgoModel *)src->d_model, g, A);
   else if (src->kind == 3)
     hipLaunchKernelGGL((sample_grid_kernel<InterpModel, true>), dim3(blocks), dim3(WAVE), 0, 0, (const InterpModel *)src->d_model, g, A);
+  else if (src->kind == 6)
+    hipLaunchKernelGGL((sample_grid_kernel<Simple3dModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const Simple3dModel *)src->d_model, g, A);
   else
     hipLaunchKernelGGL((sample_grid_kernel<ScatteredModel, true>), dim3(blocks), dim3(WAVE), 0, 0, (const ScatteredModel *)src->d_model, g, A);
   hipError_t e = hipDeviceSynchronize();
@@ -970,6 +1007,8 @@ extern "C" int srt_plasma_params(srt_model *m, int64_t n, const double *x, doubl
   else if (m->kind == 3) launch_wave_blocks(params_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
   else if (m->kind == 4)
     launch_wave_blocks(params_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
+  else if (m->kind == 6)
+    launch_wave_blocks(params_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
   std::vector<double> h(19 * n);
   HIP_OK(hipMemcpy(h.data(), dout.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -1001,6 +1040,8 @@ extern "C" int srt_dispersion(srt_model *m, int64_t n, const double *x, const do
     launch_wave_blocks(dispersion_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
   else if (m->kind == 4)
     launch_wave_blocks(dispersion_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
+  else if (m->kind == 6)
+    launch_wave_blocks(dispersion_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
   HIP_OK(hipMemcpy(out, dout.p, 10 * n * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
@@ -1042,6 +1083,8 @@ extern "C" int srt_gradients(srt_model *m, int64_t n, const double *x, const dou
     launch_wave_blocks(gradients_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, stage.p);
     HIP_OK(hipDeviceSynchronize()); // `stage` is freed at the end of this scope
   }
+  else if (m->kind == 6)
+    launch_wave_blocks(gradients_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, (double *)nullptr);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
   HIP_OK(hipMemcpy(out, dout.p, 14 * n * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
@@ -1066,6 +1109,8 @@ extern "C" int srt_rk_step(srt_model *m, int64_t n, const double *args, const do
     launch_wave_blocks(rkstep_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, stage.p);
     HIP_OK(hipDeviceSynchronize());
   }
+  else if (m->kind == 6)
+    launch_wave_blocks(rkstep_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, (double *)nullptr);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
   HIP_OK(hipMemcpy(out, dout.p, 21 * n * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
@@ -1103,13 +1148,14 @@ static void smp_eval(srt_model *src, long long n, double *rec) {
   if (n <= 0) return;
   if (src->kind == 1) launch_wave_blocks(smp_eval_kernel<NgoModel, false>, n, 0, (const NgoModel *)src->d_model, n, rec);
   else if (src->kind == 3) launch_wave_blocks(smp_eval_kernel<InterpModel, true>, n, 0, (const InterpModel *)src->d_model, n, rec);
+  else if (src->kind == 6) launch_wave_blocks(smp_eval_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)src->d_model, n, rec);
   else launch_wave_blocks(smp_eval_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)src->d_model, n, rec);
 }
 
 extern "C" int srt_build_samples(srt_model *src, const srt_sampler_params *sp, int64_t n_in, const double *in_pts,
                                  int64_t *n_out, double **out, int64_t stage_counts[6]) {
   if (!src || !sp || !n_out || !out || n_in < 0 || (n_in > 0 && !in_pts)) return srt_set_error(SRT_EINVAL, "bad argument");
-  if (src->kind != 1 && src->kind != 3 && src->kind != 4) return srt_set_error(SRT_EINVAL, "model kind %d unsupported", src->kind);
+  if (src->kind != 1 && src->kind != 3 && src->kind != 4 && src->kind != 6) return srt_set_error(SRT_EINVAL, "model kind %d unsupported", src->kind);
   const double *bd = sp->bounds;
   if (!(bd[1] > bd[0]) || !(bd[3] > bd[2]) || !(bd[5] > bd[4])) return srt_set_error(SRT_EINVAL, "empty bounds");
   if (sp->n_zero_altitude < 0 || sp->n_iri_pad < 0 || sp->n_initial_radial < 0 || sp->n_initial_uniform < 0 || sp->max_recursion < 0 ||
@@ -1369,6 +1415,9 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
   // persistent grid: enough one-wave blocks to fill the chip, never more than the rays need
   // interp: 34 KiB of LDS per wave, 512 registers per lane: one wave per SIMD; scattered: 18.5 KiB, <= 256 registers: two
+  // simple3d: as Ngo -- the default WaveBudget (one wave per SIMD).  Its density body needs 148 registers, but the integrator
+  // around it is what fills the budget: 376 .. 394 registers with the dipole field, 512 with T04_s, the same as the Ngo kernels;
+  // two waves per SIMD (256 registers) would spill the integrator's state on every trip.
   int per_cu = m->kind == 3 ? 4 : (m->kind == 4 ? 4 * ScatteredModel::WAVES_PER_EU : 8);
   if (const char *e = getenv("SRT_WAVES_PER_CU")) {
     const int v = atoi(e);
@@ -1496,6 +1545,7 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   if (m->kind == 1) SRT_LAUNCH_TRACE(NgoModel, false);
   else if (m->kind == 3) SRT_LAUNCH_TRACE(InterpModel, true);
   else if (m->kind == 4) SRT_LAUNCH_TRACE(ScatteredModel, true);
+  else if (m->kind == 6) SRT_LAUNCH_TRACE(Simple3dModel, false);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
 #undef SRT_LAUNCH_TRACE
 #undef SRT_LAUNCH_TRACE1

@@ -108,8 +108,22 @@ static int make_model(int device, srt_model **out, double *del) {
     double root = 0;
     get_real("scattered_interp_root_sample", root);
     CHECK(srt_model_create_scattered_file_root(file.c_str(), yearday, msec, ws, order, exact, lws, (int64_t)floor(root) - 1, &m));
+  } else if (modelnum == 6) {
+    // simple_3d_model_adapter (raytracer_driver.f95:893-992).  --ngo_configfile is accepted and ignored, as the driver reads
+    // it and never uses it.  Required by name (the driver would run on whatever its state block holds): kp, and MLT when
+    // fixed_MLT = 1.
+    double kp = 0.0, mlt = 0.0;
+    int fixed_mlt = 0;
+    getopt_named("ngo_configfile", file);
+    need(get_real("kp", kp), "kp");
+    get_int("fixed_MLT", fixed_mlt);
+    if (fixed_mlt == 1) need(get_real("MLT", mlt), "MLT");
+    else get_real("MLT", mlt);
+    p.del = 1.0e-6; // delDP (:1188)
+    CHECK(srt_model_create_simple3d(kp, fixed_mlt, mlt, yearday, msec, &m));
   } else {
-    fprintf(stderr, "raytracer: --modelnum=%d is not on the accelerated path (1, 3, 4 are)\n", modelnum);
+    fprintf(stderr, "raytracer: --modelnum=%d is not on the accelerated path (1, 3, 4 and 6 are; 2 = GCPM, 5 = the 3-D Ngo variant "
+                    "and 7 = AT64ThCh are out of scope)\n", modelnum);
     return 2;
   }
   if (use_igrf != 0 || use_tsy != 0) {
@@ -137,11 +151,14 @@ int main(int argc, char **argv) {
          "  --dt0 --dtmax --tmax --root --fixedstep --maxerr --maxsteps --minalt\n"
          "  --inputraysfile --outputfile --outputper\n"
          "  --modelnum  (1) Ngo model  (3) interpolated model (gridded)  (4) interpolated model (scattered)\n"
+         "              (6) simplified GCPM (closed form)\n"
          "  model 1: --ngo_configfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1 --tsyganenko_Pdyn .. _W6\n"
          "  model 3: --interp_interpfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1\n"
          "  model 4: model 3 flags + --scattered_interp_window_scale --scattered_interp_order\n"
          "           --scattered_interp_exact --scattered_interp_local_window_scale\n"
          "           [--scattered_interp_root_sample=N: record N of the file is the root of the reference's kd-tree (spacing 0)]\n"
+         "  model 6: --kp --yearday --milliseconds_day [--fixed_MLT=1 --MLT=<hours>] --use_tsyganenko=0|1 --use_igrf=0|1\n"
+         "           --tsyganenko_Pdyn .. _W6  (--ngo_configfile is accepted and ignored, as by the reference's driver)\n"
          "  extra:   --device=N | --devices=0,1,..  --chunk_rays=N  --ray_order=0|1  --timing=1 (wall clock per phase)\n"
          "           --first_attempt_policy=1|0: error estimate of a ray's first adaptive attempt, where the reference reads an\n"
          "             unset variable: 1 (default) = from the k term alone, as the reference's gfortran build behaves;\n"

@@ -43,6 +43,14 @@ module srt_bindc
        integer(c_int), value :: yearday, msec
        type(c_ptr) :: model
      end function srt_model_create_interp_file
+     ! modelnum = 6 (simple_3d_model_adapter.f95): fixed_MLT = 1 holds every point at MLT hours
+     integer(c_int) function srt_model_create_simple3d(kp, fixed_MLT, MLT, yearday, msec, model) &
+          bind(C, name="srt_model_create_simple3d")
+       import :: c_int, c_ptr, c_double
+       real(c_double), value :: kp, MLT
+       integer(c_int), value :: fixed_MLT, yearday, msec
+       type(c_ptr) :: model
+     end function srt_model_create_simple3d
      integer(c_int) function srt_model_create_scattered_file(ptsfile, yearday, msec, window_scale, order, exact, &
           local_window_scale, model) bind(C, name="srt_model_create_scattered_file")
        import :: c_int, c_char, c_ptr, c_double

@@ -73,6 +73,19 @@ def launch_set(nrays, seed):
     return np.ascontiguousarray(pos), np.ascontiguousarray(d), 2.0 * np.pi * f
 
 
+# modelnum 6 (the closed-form simplified GCPM): config[1]'s launch set -- 100 k rays, seed 2, adaptive RK45, maxsteps 512,
+# outputper 8 -- in a Kp 4 plasmasphere on 2010-01-01, MLT from each point's longitude; del = the driver's delDP
+SIMPLE3D_100K = dict(rays=100_000, seed=2, kp=4.0, yearday=2010001, msec=0, fixed_mlt=None,
+                     trace=dict(fixedstep=0, dt0=1e-3, dtmax=0.1, tmax=0.5, maxerr=5e-4, maxsteps=512, outputper=8, del_=1e-6))
+
+
+def simple3d_launch_set(nrays=None):
+    """The model-6 launch set: (pos0, dir0, w0) of SIMPLE3D_100K, or its first nrays rays."""
+    pos, d, w = launch_set(SIMPLE3D_100K["rays"], SIMPLE3D_100K["seed"])
+    n = SIMPLE3D_100K["rays"] if nrays is None else int(nrays)
+    return pos[:n], d[:n], w[:n]
+
+
 def appendix_b_rays(n=16):
     """The 16 probe rays of SURVEY.md Appendix B (explicit, non-field-aligned directions)."""
     rows = []
