@@ -7,8 +7,8 @@
  *                        raytracer_stopconditions)            (signature fortran/raytracer.f95:609-642)
  * becomes one batched call, srt_trace_batch().  The reference's plugin callback
  *     subroutine funcPlasmaParams(x, qs, Ns, ms, nus, B0, funcPlasmaParamsData)   (raytracer.f95:121-129)
- * cannot be a host callback on a GPU path; its four in-scope implementations are selected by the
- * model handle instead (modelnum 1 / 3 / 4 / 6 of raytracer_driver.f95:256-992) and are exposed for
+ * cannot be a host callback on a GPU path; its five in-scope implementations are selected by the
+ * model handle instead (modelnum 1 / 3 / 4 / 5 / 6 of raytracer_driver.f95:256-992) and are exposed for
  * point queries through srt_plasma_params().
  *
  * Conventions: plain pointers and sizes, no C++ or torch types.  All arrays are HOST memory unless a
@@ -128,6 +128,16 @@ int srt_model_create_scattered_file_root(const char *ptsfile, int yearday, int m
  * With do_cap = 0 the polar-cap code (ne_cap, poleward_edge) is dead and is not part of this library.  Where the
  * reference stops the process ("Failed to find knee in check_crossing") the densities are NaN and a traced ray ends with
  * SRT_STOP_NUMERIC. */
+/* modelnum=5: ngo_3d_dens_model_adapter.f95 + ngo_3d_dens_model.f95, the 3-D Ngo model.  Modelnum 1's diffusive-equilibrium
+ * plasmasphere, read from the same card file, with the plasmapause moved at every evaluated point to where pp_profile_d.f95's
+ * bulge puts it for the point's MLT and Kp: lk = a8(MLT, kp) - ddk, in the knee and in the sinusoidal perturbation of the ducts.
+ * The file's own lk serves only the normalisation of ane0 at setup (readinput), never a density.  MLT comes from the point's
+ * longitude, mod(24 phi / 2 pi + 12, 24); fixed_MLT = 1 holds every point at MLT hours instead.  The driver maps
+ * --ngo_configfile, --kp, --yearday, --milliseconds_day, --use_tsyganenko, --use_igrf and the ten --tsyganenko_* flags to this
+ * model (raytracer_driver.f95:772-891; the field flags go through srt_model_set_field / srt_model_set_tsyganenko_params); it
+ * never sets fixed_MLT or MLT itself, so a run of the driver is fixed_MLT = 0.  The driver's step for this model is
+ * del = 1e-6.  Kind 5, four species (electrons, H+, He+, O+). */
+int srt_model_create_ngo3d(const char *configfile, double kp, int fixed_MLT, double MLT, int yearday, int msec, srt_model **out);
 int srt_model_create_simple3d(double kp, int fixed_MLT, double MLT, int yearday, int msec, srt_model **out);
 /* The step before the path: sample a model's funcPlasmaParams on a regular nx x ny x nz grid in
  * log space ON THE DEVICE -- gcpm_dens_model_buildgrid.f95:160-300 with any model handle in place of GCPM.
@@ -175,7 +185,7 @@ int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenko, const ch
 /* parmod[10] = Pdyn (nPa), Dst (nT), ByIMF, BzIMF (nT), W1 .. W6: the driver's --tsyganenko_* flags */
 int srt_model_set_tsyganenko_params(srt_model *m, const double parmod[10]);
 void srt_model_destroy(srt_model *m);
-int srt_model_kind(const srt_model *m);  /* 1, 3, 4 or 6 */
+int srt_model_kind(const srt_model *m);  /* 1, 3, 4, 5 or 6 */
 int srt_model_nspec(const srt_model *m);
 int srt_model_species(const srt_model *m, double qs[SRT_MAXSPEC], double ms[SRT_MAXSPEC]);
 int64_t srt_model_device_bytes(const srt_model *m);

@@ -82,6 +82,7 @@ def lib():
     L.srt_model_create_scattered_file_root.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                                        C.c_double, C.c_int64, C.POINTER(vp)]
     L.srt_model_create_simple3d.argtypes = [C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
+    L.srt_model_create_ngo3d.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
     L.srt_model_set_field.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
     L.srt_model_set_tsyganenko_params.argtypes = [vp, dp]
     L.srt_model_destroy.argtypes = [vp]
@@ -220,6 +221,17 @@ class Model:
         fixed = 0 if fixed_mlt is None else 1
         _check(lib().srt_model_create_simple3d(float(kp), fixed, 0.0 if fixed_mlt is None else float(fixed_mlt), yearday,
                                                msec, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def ngo3d(cls, configfile, kp, yearday=2010001, msec=0, fixed_mlt=None):
+        """modelnum 5, the 3-D Ngo model (ngo_3d_dens_model_adapter.f95): the Ngo model of `configfile` with the plasmapause
+        of every evaluated point at a8(MLT, kp) - ddk.  fixed_mlt: None = MLT from each point's longitude (all the reference's
+        driver does); a number = every point is held at that many hours MLT."""
+        h = C.c_void_p()
+        fixed = 0 if fixed_mlt is None else 1
+        _check(lib().srt_model_create_ngo3d(os.fsencode(configfile), float(kp), fixed,
+                                            0.0 if fixed_mlt is None else float(fixed_mlt), yearday, msec, C.byref(h)))
         return cls(h)
 
     def build_grid(self, nx, ny, nz, bounds, compder=False):

@@ -14,6 +14,7 @@
 #include "../../include/srt.h"
 #include "srt_host.hpp"
 #include "srt_kernels.hpp"
+#include "srt_ngo_setup.hpp"
 #include "srt_scattered.hpp"
 #include "srt_simple3d.hpp"
 #include "srt_sampler.hpp"
@@ -138,6 +139,7 @@ struct srt_model {
   InterpModel interp{};
   ScatteredModel scat{};
   Simple3dModel s3{};
+  Ngo3dModel ngo3{};
   double *d_pts = nullptr;
   double *d_xyz = nullptr; // scattered model: the sample positions once more, SoA [3][npts] (the candidate scans read only these)
   int *d_cells = nullptr;
@@ -240,6 +242,9 @@ static int model_finish(srt_model *m) {
   } else if (m->kind == 4) {
     HIP_OK(hipMalloc(&m->d_model, sizeof(ScatteredModel)));
     HIP_OK(hipMemcpy(m->d_model, &m->scat, sizeof(ScatteredModel), hipMemcpyHostToDevice));
+  } else if (m->kind == 5) {
+    HIP_OK(hipMalloc(&m->d_model, sizeof(Ngo3dModel)));
+    HIP_OK(hipMemcpy(m->d_model, &m->ngo3, sizeof(Ngo3dModel), hipMemcpyHostToDevice));
   } else if (m->kind == 6) {
     HIP_OK(hipMalloc(&m->d_model, sizeof(Simple3dModel)));
     HIP_OK(hipMemcpy(m->d_model, &m->s3, sizeof(Simple3dModel), hipMemcpyHostToDevice));
@@ -382,74 +387,78 @@ __global__ void ngo_norm_kernel(NgoModel g, double z1, double sinz22, double lat
   out[0] = Ns[0] * 1.0e-6; // ani(1)
 }
 
-extern "C" int srt_model_create_ngo(const char *configfile, int yearday, int msec, srt_model **out) {
-  if (!configfile || !out) return srt_set_error(SRT_EINVAL, "null argument");
-  DeviceScope srt_iscope_;
-  int rc = srt_iscope_.enter_default();
-  if (rc) return rc;
+// readinput (ngo_dens_model.f95:29-160; ngo_3d_dens_model.f95 has the same): the card file and the normalisation of ane0
+static int ngo_readinput(const char *configfile, NgoModel &g) {
   srt_host::NgoConfig cfg;
   std::string err;
   if (!srt_host::read_newray(configfile, cfg, err)) return srt_set_error(SRT_EIO, "%s: %s", configfile, err.c_str());
-  srt_model *m = new srt_model;
-  m->kind = 1;
-  m->nspec = 4;
-  NgoModel &g = m->ngo;
-  memset(&g, 0, sizeof g);
-  g.r0 = 6370.0;
-  g.pi32 = (double)3.141592653589793f; // default-real literal, ngo_dens_model.f95:36 (SURVEY A-6)
-  g.num = cfg.num;
-  g.kducts = cfg.kducts;
-  g.kinit = 2;
-  g.therm = cfg.therm;
-  g.rbase = cfg.rbase;
-  g.ane0 = cfg.ane0;
-  for (int i = 0; i < 5; ++i) g.alpha0[i] = cfg.alpha0[i];
-  g.rzero = cfg.rzero;
-  g.scbot = cfg.scbot;
-  g.lk = cfg.lk;
-  g.expk = cfg.expk;
-  g.ddk = cfg.ddk;
-  g.rconsn = cfg.rconsn;
-  g.scr = cfg.scr;
-  for (int k = 0; k < 10; ++k) {
-    g.l0[k] = cfg.l0[k]; g.def[k] = cfg.def[k]; g.dd[k] = cfg.dd[k];
-    g.rducln[k] = cfg.rducln[k]; g.rducun[k] = cfg.rducun[k];
-    g.rducls[k] = cfg.rducls[k]; g.rducus[k] = cfg.rducus[k];
-    g.sidedu[k] = cfg.sidedu[k];
-    g.hl2n[k] = cfg.hducln[k] * cfg.hducln[k]; g.hl2s[k] = cfg.hducls[k] * cfg.hducls[k];
-    g.hu2n[k] = cfg.hducun[k] * cfg.hducun[k]; g.hu2s[k] = cfg.hducus[k] * cfg.hducus[k];
-  }
-  // ane0 <- ane0*dsdens/ani(1) at (dsrrng, dsrlat)  (:120-123); grarad is built on the float32 pi
-  double radgra = 180.0 / g.pi32, grarad = 1.0 / radgra;
-  double z2 = (90.0 - cfg.dsrlat) * grarad;
-  double z1 = cfg.dsrrng * g.r0;
-  double s2 = sin(z2);
+  ngo_fill(cfg, g);
+  double z1, sinz22;
+  ngo_norm_point(cfg, g, z1, sinz22);
   double *d_out = nullptr;
   double ani1 = 0.0;
-  if (hipMalloc(&d_out, sizeof(double)) != hipSuccess) {
-    delete m;
-    return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-  }
-  // the latitude dens() sees during this call is the last satellite latitude read (:64)
-  hipLaunchKernelGGL(ngo_norm_kernel, dim3(1), dim3(1), 0, 0, g, z1, s2 * s2, cfg.last_latitu, d_out);
+  if (hipMalloc(&d_out, sizeof(double)) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  hipLaunchKernelGGL(ngo_norm_kernel, dim3(1), dim3(1), 0, 0, g, z1, sinz22, cfg.last_latitu, d_out);
   hipError_t e = hipMemcpy(&ani1, d_out, sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(d_out);
-  if (e != hipSuccess) {
-    delete m;
-    return srt_set_error(SRT_EDEVICE, "ngo normalisation kernel failed: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "ngo normalisation kernel failed: %s", hipGetErrorString(e));
   g.ane0 = g.ane0 * cfg.dsdens / ani1;
+  return SRT_OK;
+}
+
+// species constants of both Ngo adapters (ngo_dens_model_adapter.f95:136-138, ngo_3d_dens_model_adapter.f95:173-175), the
+// field tail's date, and the device copies
+static int ngo_finish(srt_model *m, int yearday, int msec, srt_model **out) {
   const double e_ = 1.602e-19;
   double qs[4] = {e_ * -1.0, e_, e_, e_};
   double ms[4] = {9.10938188e-31, 1.6726e-27, 4.0 * 1.6726e-27, 16.0 * 1.6726e-27};
   fill_common(m->cm, 4, qs, ms, yearday, msec);
-  rc = model_finish(m);
+  const int rc = model_finish(m);
   if (rc) {
     srt_model_destroy(m);
     return rc;
   }
   *out = m;
   return SRT_OK;
+}
+
+extern "C" int srt_model_create_ngo(const char *configfile, int yearday, int msec, srt_model **out) {
+  if (!configfile || !out) return srt_set_error(SRT_EINVAL, "null argument");
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  srt_model *m = new srt_model;
+  m->kind = 1;
+  m->nspec = 4;
+  rc = ngo_readinput(configfile, m->ngo);
+  if (rc) {
+    delete m;
+    return rc;
+  }
+  return ngo_finish(m, yearday, msec, out);
+}
+
+// ---- ngo3d: the Ngo model with the plasmapause of each evaluated point from bulge(MLT, Kp) (srt_ngo3d.hpp) ------
+extern "C" int srt_model_create_ngo3d(const char *configfile, double kp, int fixed_MLT, double MLT, int yearday, int msec,
+                                      srt_model **out) {
+  if (!configfile || !out) return srt_set_error(SRT_EINVAL, "null argument");
+  if (fixed_MLT != 0 && fixed_MLT != 1) return srt_set_error(SRT_EINVAL, "fixed_MLT must be 0 or 1");
+  if (!std::isfinite(kp) || (fixed_MLT == 1 && !std::isfinite(MLT))) return srt_set_error(SRT_EINVAL, "kp and MLT must be finite");
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  srt_model *m = new srt_model;
+  m->kind = 5;
+  m->nspec = 4;
+  rc = ngo_readinput(configfile, m->ngo3.ngo); // ane0 is normalised with the file's lk (readinput runs once, at setup)
+  if (rc) {
+    delete m;
+    return rc;
+  }
+  m->ngo3.kp = kp;
+  m->ngo3.fixed_mlt = fixed_MLT;
+  m->ngo3.mlt = MLT;
+  return ngo_finish(m, yearday, msec, out);
 }
 
 // ---- simple3d: closed form, nothing but a handful of constants (srt_simple3d.hpp) -------------------
@@ -792,6 +801,8 @@ static int sample_model_on_grid(srt_model *src, int compder, int nx, int ny, int
     hipLaunchKernelGGL((sample_grid_kernel<NgoModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const NgoModel *)src->d_model, g, A);
   else if (src->kind == 3)
     hipLaunchKernelGGL((sample_grid_kernel<InterpModel, true>), dim3(blocks), dim3(WAVE), 0, 0, (const InterpModel *)src->d_model, g, A);
+  else if (src->kind == 5)
+    hipLaunchKernelGGL((sample_grid_kernel<Ngo3dModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const Ngo3dModel *)src->d_model, g, A);
   else if (src->kind == 6)
     hipLaunchKernelGGL((sample_grid_kernel<Simple3dModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const Simple3dModel *)src->d_model, g, A);
   else
@@ -1007,6 +1018,8 @@ extern "C" int srt_plasma_params(srt_model *m, int64_t n, const double *x, doubl
   else if (m->kind == 3) launch_wave_blocks(params_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
   else if (m->kind == 4)
     launch_wave_blocks(params_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
+  else if (m->kind == 5)
+    launch_wave_blocks(params_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
   else if (m->kind == 6)
     launch_wave_blocks(params_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
@@ -1040,6 +1053,8 @@ extern "C" int srt_dispersion(srt_model *m, int64_t n, const double *x, const do
     launch_wave_blocks(dispersion_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
   else if (m->kind == 4)
     launch_wave_blocks(dispersion_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
+  else if (m->kind == 5)
+    launch_wave_blocks(dispersion_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
   else if (m->kind == 6)
     launch_wave_blocks(dispersion_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
@@ -1083,6 +1098,8 @@ extern "C" int srt_gradients(srt_model *m, int64_t n, const double *x, const dou
     launch_wave_blocks(gradients_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, stage.p);
     HIP_OK(hipDeviceSynchronize()); // `stage` is freed at the end of this scope
   }
+  else if (m->kind == 5)
+    launch_wave_blocks(gradients_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, (double *)nullptr);
   else if (m->kind == 6)
     launch_wave_blocks(gradients_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, (double *)nullptr);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
@@ -1109,6 +1126,8 @@ extern "C" int srt_rk_step(srt_model *m, int64_t n, const double *args, const do
     launch_wave_blocks(rkstep_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, stage.p);
     HIP_OK(hipDeviceSynchronize());
   }
+  else if (m->kind == 5)
+    launch_wave_blocks(rkstep_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, (double *)nullptr);
   else if (m->kind == 6)
     launch_wave_blocks(rkstep_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, (double *)nullptr);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
@@ -1148,6 +1167,7 @@ static void smp_eval(srt_model *src, long long n, double *rec) {
   if (n <= 0) return;
   if (src->kind == 1) launch_wave_blocks(smp_eval_kernel<NgoModel, false>, n, 0, (const NgoModel *)src->d_model, n, rec);
   else if (src->kind == 3) launch_wave_blocks(smp_eval_kernel<InterpModel, true>, n, 0, (const InterpModel *)src->d_model, n, rec);
+  else if (src->kind == 5) launch_wave_blocks(smp_eval_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)src->d_model, n, rec);
   else if (src->kind == 6) launch_wave_blocks(smp_eval_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)src->d_model, n, rec);
   else launch_wave_blocks(smp_eval_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)src->d_model, n, rec);
 }
@@ -1155,7 +1175,7 @@ static void smp_eval(srt_model *src, long long n, double *rec) {
 extern "C" int srt_build_samples(srt_model *src, const srt_sampler_params *sp, int64_t n_in, const double *in_pts,
                                  int64_t *n_out, double **out, int64_t stage_counts[6]) {
   if (!src || !sp || !n_out || !out || n_in < 0 || (n_in > 0 && !in_pts)) return srt_set_error(SRT_EINVAL, "bad argument");
-  if (src->kind != 1 && src->kind != 3 && src->kind != 4 && src->kind != 6) return srt_set_error(SRT_EINVAL, "model kind %d unsupported", src->kind);
+  if (src->kind != 1 && src->kind != 3 && src->kind != 4 && src->kind != 5 && src->kind != 6) return srt_set_error(SRT_EINVAL, "model kind %d unsupported", src->kind);
   const double *bd = sp->bounds;
   if (!(bd[1] > bd[0]) || !(bd[3] > bd[2]) || !(bd[5] > bd[4])) return srt_set_error(SRT_EINVAL, "empty bounds");
   if (sp->n_zero_altitude < 0 || sp->n_iri_pad < 0 || sp->n_initial_radial < 0 || sp->n_initial_uniform < 0 || sp->max_recursion < 0 ||
@@ -1415,6 +1435,7 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
   // persistent grid: enough one-wave blocks to fill the chip, never more than the rays need
   // interp: 34 KiB of LDS per wave, 512 registers per lane: one wave per SIMD; scattered: 18.5 KiB, <= 256 registers: two
+  // ngo3d: the Ngo kernels with a plasmapause head per point; the default WaveBudget, as Ngo
   // simple3d: as Ngo -- the default WaveBudget (one wave per SIMD).  Its density body needs 148 registers, but the integrator
   // around it is what fills the budget: 376 .. 394 registers with the dipole field, 512 with T04_s, the same as the Ngo kernels;
   // two waves per SIMD (256 registers) would spill the integrator's state on every trip.
@@ -1545,6 +1566,7 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   if (m->kind == 1) SRT_LAUNCH_TRACE(NgoModel, false);
   else if (m->kind == 3) SRT_LAUNCH_TRACE(InterpModel, true);
   else if (m->kind == 4) SRT_LAUNCH_TRACE(ScatteredModel, true);
+  else if (m->kind == 5) SRT_LAUNCH_TRACE(Ngo3dModel, false);
   else if (m->kind == 6) SRT_LAUNCH_TRACE(Simple3dModel, false);
   else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
 #undef SRT_LAUNCH_TRACE

@@ -122,8 +122,9 @@ static int make_model(int device, srt_model **out, double *del) {
     p.del = 1.0e-6; // delDP (:1188)
     CHECK(srt_model_create_simple3d(kp, fixed_mlt, mlt, yearday, msec, &m));
   } else {
-    fprintf(stderr, "raytracer: --modelnum=%d is not on the accelerated path (1, 3, 4 and 6 are; 2 = GCPM, 5 = the 3-D Ngo variant "
-                    "and 7 = AT64ThCh are out of scope)\n", modelnum);
+    fprintf(stderr, "raytracer: --modelnum=%d is not on the accelerated path (1, 3, 4 and 6 are; 5 = the 3-D Ngo model is in the "
+                    "library, srt_model_create_ngo3d, and not yet reachable from this executable; 2 = GCPM and 7 = AT64ThCh are "
+                    "out of scope)\n", modelnum);
     return 2;
   }
   if (use_igrf != 0 || use_tsy != 0) {

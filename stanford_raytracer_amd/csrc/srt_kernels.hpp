@@ -7,6 +7,7 @@
 // until the queue is empty -- every wave reaches that exit.
 #pragma once
 #include "srt_models.hpp"
+#include "srt_ngo3d.hpp"
 
 namespace srt {
 
@@ -107,7 +108,7 @@ __device__ __noinline__ double offset_F(const CM &cm, double px, double py, doub
 #endif
 template <class M>
 constexpr bool spread_rhs() {
-  return (SRT_NGO_SPREAD != 0 && std::is_same<M, NgoModel>::value) || (SRT_INTERP_SPREAD != 0 && std::is_same<M, InterpModel>::value);
+  return (SRT_NGO_SPREAD != 0 && (std::is_same<M, NgoModel>::value || std::is_same<M, Ngo3dModel>::value)) || (SRT_INTERP_SPREAD != 0 && std::is_same<M, InterpModel>::value);
 }
 // the exchange area of the spread right-hand sides: ONE allocation per kernel, whichever call sites use it
 struct SpreadLds {

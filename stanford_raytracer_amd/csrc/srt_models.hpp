@@ -7,6 +7,9 @@
 #pragma once
 #include "srt_device.hpp"
 
+// bodies that also compile for the host (tests/native/ngo3d_host.cpp builds the Ngo density path on the CPU)
+#define SRT_HD __host__ __device__
+
 namespace srt {
 
 constexpr int WAVE = 64;
@@ -101,7 +104,7 @@ struct NgoModel {
   int num, kducts, kinit;
 
   // noinline: ONE compiled body, so that a point gets the same arithmetic whichever path (and lane) evaluates it
-  __device__ __noinline__ void dens_point(double x, double y, double z, double Ns[4]) const {
+  SRT_HD __noinline__ void dens_point(double x, double y, double z, double Ns[4]) const {
     double rho2 = x * x + y * y;
     double r2 = rho2 + z * z;
     double r = sqrt(r2);
@@ -110,7 +113,12 @@ struct NgoModel {
   }
 
   // dens (ngo_dens_model.f95:165-353) entered with z(1), sin^2 z(2) and the latitude
-  __device__ inline void dens_core(double z1, double sinz22, double latitu, double Ns[4]) const {
+  SRT_HD inline void dens_core(double z1, double sinz22, double latitu, double Ns[4]) const { dens_core_at<false>(z1, sinz22, latitu, lk, Ns); }
+  // The bodies that read the plasmapause take it as an argument, lkp: modelnum 1 passes the file's lk, modelnum 5 (Ngo3dModel,
+  // srt_ngo3d.hpp) the value of the evaluated point.  AT selects nothing but which out-of-line copy of ducts is called -- with
+  // the member (ducts) or with the argument (ducts_at) -- so that modelnum 1's kernels keep the instructions they had.
+  template <bool AT>
+  SRT_HD inline void dens_core_at(double z1, double sinz22, double latitu, double lkp, double Ns[4]) const {
     // scale heights (:180-186); 1.150600 is a default-real literal (SURVEY A-6)
     double rb7370 = rbase / 7370.0;
     double sh2 = (double)1.150600f * therm * rb7370 * rb7370;
@@ -127,7 +135,7 @@ struct NgoModel {
     double l = z1 / (r0 * sinz22);
     double ani1 = ane0 * anr * anli;
     if (kducts != 0) {
-      double deltal = l - lk;
+      double deltal = l - lkp;
       if (!(deltal < 0.0)) { // plasmapause (:218-239)
         double d2 = ddk * ddk;
         double argl = deltal * deltal / (d2 * 2.0);
@@ -140,7 +148,7 @@ struct NgoModel {
         double trmodl = trm + (1.0 - trm) * fr;
         ani1 *= f + trmodl * (1.0 - f);
       }
-      if (kducts != 1) ani1 *= ducts(l, z1, latitu);
+      if (kducts != 1) ani1 *= AT ? ducts_at(l, z1, latitu, lkp) : ducts(l, z1, latitu);
     }
     double invq = 1.0 / q;
     Ns[0] = 1.0e6 * ani1;
@@ -151,7 +159,7 @@ struct NgoModel {
 
   // altitude taper shared by the sinusoidal perturbation and the ducts (:250-276, :299-327).
   // Returns false when the contribution is skipped entirely (arglr >= 75).
-  __device__ inline bool taper(int kd, double z1, double latitu, bool north_first, double &delnl) const {
+  SRT_HD inline bool taper(int kd, double z1, double latitu, bool north_first, double &delnl) const {
     bool lower;
     if (north_first)
       lower = (latitu >= 0 && z1 <= rducun[kd]) || (latitu <= 0 && z1 <= rducus[kd]);
@@ -194,15 +202,17 @@ struct NgoModel {
     return true;
   }
 
-  __device__ __noinline__ double ducts(double l, double z1, double latitu) const {
+  SRT_HD __noinline__ double ducts(double l, double z1, double latitu) const { return ducts_body(l, z1, latitu, lk); }
+  SRT_HD __noinline__ double ducts_at(double l, double z1, double latitu, double lkp) const { return ducts_body(l, z1, latitu, lkp); }
+  SRT_HD inline double ducts_body(double l, double z1, double latitu, double lkp) const {
     double fac = 1.0;
     int kstart = kinit;
     if (!(l0[2] > 0.0)) { // sinusoidal density perturbation (:241-288)
       kstart = 3;
       double dl = l + l0[2];
       if (!(dl * sidedu[2] >= 0.0)) dl = 0.0;
-      double delk = -l0[2] - (lk + ddk) + dd[2] / 2;
-      double critl = (lk + ddk) + fmod(delk, dd[2]);
+      double delk = -l0[2] - (lkp + ddk) + dd[2] / 2;
+      double critl = (lkp + ddk) + fmod(delk, dd[2]);
       if (!(l <= critl)) {
         double argl = 2.0 * pi32 * dl / dd[2];
         double delnl = (def[2] / 2.0) * (1.0 + cos(argl));
@@ -239,8 +249,9 @@ struct NgoModel {
     const double rhoa = ax * ax + ay * ay, ra2 = rhoa + az * az, ra = sqrt(ra2);
     const double rhob = bx * bx + by * by, rb2 = rhob + bz * bz, rb = sqrt(rb2);
     const double z1[2] = {r0 * ra / R_E, r0 * rb / R_E}, s2[2] = {rhoa / ra2, rhob / rb2}, lat[2] = {az, bz};
+    const double lk2[2] = {lk, lk};
     double N[2][4];
-    dens_core2(z1, s2, lat, N);
+    dens_core2<false>(z1, s2, lat, lk2, N);
 #pragma unroll
     for (int s = 0; s < 4; ++s) r.a[s] = N[0][s], r.b[s] = N[1][s];
     return r;
@@ -248,7 +259,9 @@ struct NgoModel {
   // dens_core for two points, statement by statement, so that the two dependent chains sit in the same basic blocks and
   // interleave: the plasmapause term (taken when deltal >= 0 in the Fortran, :218-239) is evaluated for both points and
   // selected -- the same values as the branch gives.  The operations and their order per point are those of dens_core.
-  __device__ __forceinline__ void dens_core2(const double (&z1)[2], const double (&sinz22)[2], const double (&latitu)[2], double (&Ns)[2][4]) const {
+  template <bool AT>
+  __device__ __forceinline__ void dens_core2(const double (&z1)[2], const double (&sinz22)[2], const double (&latitu)[2], const double (&lkp)[2],
+                                             double (&Ns)[2][4]) const {
     const double rb7370 = rbase / 7370.0;
     const double sh2 = (double)1.150600f * therm * rb7370 * rb7370;
     double q2[2], q3[2], q4[2], q[2], ani1[2], l[2];
@@ -270,7 +283,7 @@ struct NgoModel {
     if (kducts != 0) { // wave-uniform
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        const double deltal = l[p] - lk;
+        const double deltal = l[p] - lkp[p];
         const double d2 = ddk * ddk;
         double argl = deltal * deltal / (d2 * 2.0);
         if (!(argl < 80.0)) argl = 80.0;
@@ -285,7 +298,7 @@ struct NgoModel {
       }
       if (kducts != 1) {
 #pragma unroll
-        for (int p = 0; p < 2; ++p) ani1[p] *= ducts(l[p], z1[p], latitu[p]);
+        for (int p = 0; p < 2; ++p) ani1[p] *= AT ? ducts_at(l[p], z1[p], latitu[p], lkp[p]) : ducts(l[p], z1[p], latitu[p]);
       }
     }
 #pragma unroll
@@ -314,10 +327,15 @@ struct NgoModel {
   // stops after 29 steps), each doing its 7-8 density evaluations one after the other while most lanes idle.  When at most
   // 16 lanes of the wave need a stencil, the k-th needy lane's points are spread over lanes 4k .. 4k+3 -- one dens_pair per lane
   // instead of four in a row -- and handed back through LDS.  Same function, same arguments, another lane: bit-identical
-  // results.
+  // results.  (M: the model whose dens_pair evaluates the points -- this one or modelnum 5's, which has the same stencil.)
   template <int NE>
   __device__ __forceinline__ void density_stencil(const double c[3], const double d[3], const double *extra,
                                                   double (&Ns)[7 + NE][4], double *, bool need = true) const {
+    stencil_of<NE>(*this, c, d, extra, Ns, need);
+  }
+  template <int NE, class M>
+  __device__ __forceinline__ static void stencil_of(const M &m, const double c[3], const double d[3], const double *extra,
+                                                    double (&Ns)[7 + NE][4], bool need) {
     const unsigned long long needy = __ballot(need);
     const int nneedy = __popcll(needy);
     if (nneedy >= 1 && nneedy <= 16) { // wave-uniform
@@ -341,7 +359,7 @@ struct NgoModel {
       stencil_point<NE>(2 * sub, oc, od, oe, qa);
       stencil_point<NE>(2 * sub + 1, oc, od, oe, qb);
       SRT_TTM(11);
-      const Dens2 mine = dens_pair(qa[0], qa[1], qa[2], qb[0], qb[1], qb[2]);
+      const Dens2 mine = m.dens_pair(qa[0], qa[1], qa[2], qb[0], qb[1], qb[2]);
       SRT_TTM(12);
       // hand-off through LDS: every lane parks its two points' densities (64 B), the owners read their 7-8 points back as
       // 128-bit words -- 16 LDS reads; per-lane-indexed cross-lane reads (64 ds_bpermute) measured 7 % slower on the launch,
@@ -372,7 +390,7 @@ struct NgoModel {
       double qa[3], qb[3];
       stencil_point<NE>(2 * h, c, d, oe, qa);
       stencil_point<NE>(2 * h + 1, c, d, oe, qb);
-      const Dens2 r = dens_pair(qa[0], qa[1], qa[2], qb[0], qb[1], qb[2]);
+      const Dens2 r = m.dens_pair(qa[0], qa[1], qa[2], qb[0], qb[1], qb[2]);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         Ns[2 * h][s] = r.a[s];

@@ -43,6 +43,16 @@ module srt_bindc
        integer(c_int), value :: yearday, msec
        type(c_ptr) :: model
      end function srt_model_create_interp_file
+     ! modelnum = 5 (ngo_3d_dens_model_adapter.f95): the Ngo model with the plasmapause of each point at a8(MLT, kp) - ddk;
+     ! fixed_MLT = 1 holds every point at MLT hours (the reference's driver never sets it)
+     integer(c_int) function srt_model_create_ngo3d(configfile, kp, fixed_MLT, MLT, yearday, msec, model) &
+          bind(C, name="srt_model_create_ngo3d")
+       import :: c_int, c_char, c_ptr, c_double
+       character(kind=c_char), intent(in) :: configfile(*)
+       real(c_double), value :: kp, MLT
+       integer(c_int), value :: fixed_MLT, yearday, msec
+       type(c_ptr) :: model
+     end function srt_model_create_ngo3d
      ! modelnum = 6 (simple_3d_model_adapter.f95): fixed_MLT = 1 holds every point at MLT hours
      integer(c_int) function srt_model_create_simple3d(kp, fixed_MLT, MLT, yearday, msec, model) &
           bind(C, name="srt_model_create_simple3d")

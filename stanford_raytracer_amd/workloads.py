@@ -86,6 +86,19 @@ def simple3d_launch_set(nrays=None):
     return pos[:n], d[:n], w[:n]
 
 
+# modelnum 5 (the 3-D Ngo model): config[1]'s launch set and integrator settings again, the plasmapause file, Kp 4, MLT from each
+# point's longitude (all the reference's driver does); del = the driver's delDP
+NGO3D_100K = dict(rays=100_000, seed=2, newray=NEWRAY_PLASMAPAUSE, kp=4.0, yearday=2010001, msec=0, fixed_mlt=None,
+                  trace=dict(fixedstep=0, dt0=1e-3, dtmax=0.1, tmax=0.5, maxerr=5e-4, maxsteps=512, outputper=8, del_=1e-6))
+
+
+def ngo3d_launch_set(nrays=None):
+    """The model-5 launch set: (pos0, dir0, w0) of NGO3D_100K, or its first nrays rays."""
+    pos, d, w = launch_set(NGO3D_100K["rays"], NGO3D_100K["seed"])
+    n = NGO3D_100K["rays"] if nrays is None else int(nrays)
+    return pos[:n], d[:n], w[:n]
+
+
 def appendix_b_rays(n=16):
     """The 16 probe rays of SURVEY.md Appendix B (explicit, non-field-aligned directions)."""
     rows = []

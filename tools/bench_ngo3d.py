@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""Kernel time of the modelnum-5 trace kernel (the 3-D Ngo model) on its workloads.py launch set (config[1]'s 100 k rays, the
+plasmapause file, Kp 4), and of the Ngo kernel on the same rays, with the same file, in the same run.  HIP-event kernel time (srt_last_kernel_ms), five launches after a warm-up; inputs
+and outputs resident in HBM (DeviceBatch, the entry point bench.py times).  Prints one JSON line.
+
+    python tools/bench_ngo3d.py [--rays N] [--launches 5] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+
+def time_model(model, p, rays, launches):
+    import torch
+    from stanford_raytracer_amd.device_batch import DeviceBatch
+
+    b = DeviceBatch(model, p, *rays, device=torch.device("cuda:0"))
+    ms, steps = [], 0
+    for k in range(launches + 1):  # launch 0 warms up
+        o = b.launch()
+        torch.cuda.synchronize()
+        if k:
+            ms.append(model.last_kernel_ms())
+            steps = int(o["cnt"][1].item())
+    stop = np.bincount(o["stop"].cpu().numpy(), minlength=10).tolist()
+    med = float(np.median(ms))
+    return {"kernel_ms": [round(v, 3) for v in ms], "kernel_ms_median": round(med, 3), "accepted_steps": steps,
+            "steps_per_s": round(steps / (med * 1e-3), 1), "stop_histogram": stop}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rays", type=int, default=None)
+    ap.add_argument("--launches", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch  # before the library, as in bench.py: torch brings up its own HIP runtime first
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_ngo3d.py needs an MI355X (no CPU fallback)")
+    torch.cuda.set_device(0)
+    from stanford_raytracer_amd import api, workloads as wl
+
+    api.init(0)
+    W = wl.NGO3D_100K
+    rays = wl.ngo3d_launch_set(a.rays)
+    res = {"workload": "ngo3d_100k", "rays": int(len(rays[2])), "device": api.device_info()["name"], "trace": W["trace"]}
+    p = api.make_params(minalt=wl.MINALT, **W["trace"])
+    with tempfile.TemporaryDirectory() as d:
+        cfg = os.path.join(d, "newray.in")
+        with open(cfg, "w") as f:
+            f.write(W["newray"])
+        m5 = api.Model.ngo3d(cfg, W["kp"], yearday=W["yearday"], msec=W["msec"], fixed_mlt=W["fixed_mlt"])
+        # the Ngo kernel on the same rays (config[1]'s model; its own FD step, the driver's delSP)
+        ngo = api.Model.ngo(cfg, W["yearday"], W["msec"])
+    res["ngo3d"] = time_model(m5, p, rays, a.launches)
+    pn = api.make_params(minalt=wl.MINALT, **dict(W["trace"], del_=1e-4))
+    res["ngo_same_rays"] = time_model(ngo, pn, rays, a.launches)
+    res["ngo3d_over_ngo_ms_per_step"] = round((res["ngo3d"]["kernel_ms_median"] / res["ngo3d"]["accepted_steps"]) /
+                                              (res["ngo_same_rays"]["kernel_ms_median"] / res["ngo_same_rays"]["accepted_steps"]), 3)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
