@@ -60,7 +60,30 @@ def build(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     build_fortran(force, verbose)
+    build_probe(force, verbose)
     return LIB
+
+
+PROBE = os.path.join(LIBDIR, "libsrt_fastmath_probe.so")
+PROBE_DIR = os.path.join(PKG, "..", "tests", "native")
+PROBE_SRCS = ["fastmath_probe.hip"]
+PROBE_HDRS = ["fastmath_ops.hpp"]
+
+
+def build_probe(force=False, verbose=False):
+    """The test probe of the device-only elementary functions (tests/native/fastmath_probe.hip, for
+    tests/test_gpu_fastmath.py): a library of its own with the library's flags.  libsrt_hip.so is not linked against it."""
+    srcs = [os.path.abspath(os.path.join(PROBE_DIR, f)) for f in PROBE_SRCS]
+    if not all(os.path.exists(s) for s in srcs):
+        return None
+    os.makedirs(LIBDIR, exist_ok=True)
+    deps = srcs + [os.path.abspath(os.path.join(PROBE_DIR, f)) for f in PROBE_HDRS] + _headers() + [os.path.abspath(__file__)]
+    if force or _stale(PROBE, deps):
+        cmd = [_hipcc(), "-O3", "--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-shared", "-o", PROBE] + srcs
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return PROBE
 
 
 FDRV = os.path.join(BINDIR, "srt_fortran_driver")

@@ -10,10 +10,23 @@ constexpr double FM_PI = 3.14159265358979323846;
 // a/b for operands well inside the exponent range (every division of the hot path: frequencies, densities,
 // field magnitudes, grid spacings).  This is the compiler's own fp64 division sequence -- v_rcp_f64, two Newton
 // steps on the reciprocal, quotient, one residual correction -- without the v_div_scale / v_div_fmas /
-// v_div_fixup wrapper that only matters for operands or quotients near the ends of the exponent range, so the
-// result is bit-identical to a/b wherever that wrapper would not have scaled (8 instructions instead of 11).
+// v_div_fixup wrapper that only matters for operands or quotients near the ends of the exponent range (8 instructions
+// instead of 11).  Measured on the device (tests/test_gpu_fastmath.py): equal to the device's a / b and to IEEE a / b on
+// every one of 1.2e6 points with the exponents of a and b in [-250, 250], edge mantissas and quotients next to rounding ties
+// included (equal as numbers: the sign of a zero quotient can differ, -0 / 3 gives +0); the same test prints where it leaves IEEE
+// outside that box.
 // The sequence in two halves, so that divisions by the same b share the first: fdiv_recip(b) is the refined reciprocal (it
 // depends on b alone), fdiv_r(a, b, r) the quotient and its correction.  fdiv(a, b) == fdiv_r(a, b, fdiv_recip(b)) bit for bit.
+//
+// OUTSIDE THE DOMAINS (pinned by tests/fastmath_cases.py::OUTSIDE on the device and in the host emulation; change both together):
+//   fdiv      b = +-0, b = +-inf, b denormal, a = +-inf, an overflowing quotient (1e300 / 1e-300), NaN in a or b   -> NaN
+//             (IEEE: +-inf, +-0, a finite or infinite quotient)
+//   sqrt_pos  x < 0, x = +inf, NaN -> NaN;  x = -0 -> +0
+//   log_pos   x < 0, x = +inf, NaN -> NaN;  x = +-0 -> -4.7507062... (a finite number, NOT -inf)
+//   exp_any   NaN -> 0 (fmax drops the NaN);  -inf -> 0;  +inf -> NaN;  y <= -745.2 -> 0;  y >= 709.79 -> +inf
+//   sincos_0pi  +-inf -> (-inf, NaN);  NaN -> (NaN, NaN)
+//   sincos_mod  +-inf, NaN -> (NaN, NaN)
+//   pow_pos   x <= 0, x >= 1e300, x NaN: the library's pow;  otherwise y NaN or +-inf -> NaN
 __device__ __forceinline__ double fdiv_recip(double b) {
   double r = __builtin_amdgcn_rcp(b);
   r = fma(fma(-b, r, 1.0), r, r);
@@ -28,11 +41,16 @@ __device__ __forceinline__ double fdiv(double a, double b) { return fdiv_r(a, b,
 
 // Elementary functions on the argument ranges of the scattered model's per-sample passes (srt_scattered.hpp) and of the
 // T04_s field (srt_t04.hpp): each is the textbook (fdlibm) kernel without the library's range handling -- arguments there
-// are never denormal, huge or NaN-by-construction -- and agrees with the library to <= 1-2 ulp, at a third to a half of
-// its instructions.
+// are never denormal, huge or NaN-by-construction -- at a third to a half of the library's instructions.  Largest errors
+// measured on the device against long double, in ulp of the true value (tests/test_gpu_fastmath.py; the bar there is 2 ulp;
+// tests/test_fastmath_host.py holds this header on the host, exact 1/b and 1/sqrt(x) for the hardware's seeds, to the same):
+// sqrt_pos correctly rounded; sqrt_and_inv_pos 0.50 / 1.48; sincos_0pi 1.29 / 1.39; log_pos 0.72; exp_any 0.88 (0.87 of the
+// denormal spacing below -708.4); sincos_mod 1.44 / 1.45; pow_pos 0.66.  Next to a zero of sin or cos the two-part pi/2 leaves
+// an absolute error of (|k| + 1) 6.5e-27 (k the quadrant), not a relative one.
 namespace fm {
 // sqrt for 0 <= x, neither denormal nor near overflow: the compiler's own sequence (v_rsq_f64, one Goldschmidt step, two
-// residual corrections) without its range scaling
+// residual corrections) without its range scaling; equal to the device's sqrt and correctly rounded on exponents in
+// [-500, 500] (measured; the residual goes denormal below about 2^-960)
 __device__ __forceinline__ double sqrt_pos(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
@@ -138,10 +156,68 @@ __device__ __forceinline__ double cos_mod(double x) {
   sincos_mod(x, s, c);
   return c;
 }
-// x**y for x > 0 (relative error ~|y ln x| 2^-52); x <= 0 or not finite: the library's
+// ln x = hi + lo for a positive normal x, to an absolute error of about 2^-60 (log_pos: half an ulp of the result, up to 2^-44).
+// The reduction and the polynomial of log_pos, written as k ln2 + 2 s + s R(s^2) with s = f / (2 + f): k ln2_hi and 2 s_hi are
+// summed exactly (Fast2Sum, |k ln2_hi| >= |2 s_hi| or k == 0), everything small -- the division's remainder, the rounding of
+// 2 + f, s R and k ln2_lo -- goes into lo; |lo| <= ulp(hi) / 2 after the final renormalisation.
+__device__ __forceinline__ void log_pos_hilo(double x, double &hi, double &lo) {
+  double m = __builtin_amdgcn_frexp_mant(x); // [0.5, 1)
+  int e = __builtin_amdgcn_frexp_exp(x);
+  const bool low = m < 0.70710678118654752440;
+  m = low ? m + m : m; // [sqrt(1/2), sqrt 2)
+  e = low ? e - 1 : e;
+  const double f = m - 1.0, k = (double)e;
+  const double t = 2.0 + f, tl = (2.0 - t) + f; // 2 + f = t + tl exactly
+  const double rc = fdiv_recip(t);
+  const double sh = fdiv_r(f, t, rc);
+  const double sl = fma(-sh, tl, fma(-sh, t, f)) * rc; // f / (t + tl) = sh + sl
+  const double z = sh * sh, w = z * z;
+  const double t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01));
+  const double t2 = z * (6.666666666666735130e-01 + w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 + w * 1.479819860511658591e-01)));
+  const double A = k * 6.93147180369123816490e-01, B = sh + sh; // both exact
+  const double small = fma(k, 1.90821492927058770002e-10, fma(sh, t2 + t1, sl + sl));
+  const double h0 = A + B, l0 = ((A - h0) + B) + small;
+  hi = h0 + l0;
+  lo = (h0 - hi) + l0;
+}
+// e^(h + l) for |l| <= ~1e-10 |h|, h <= ~700, to 0.5 ulp + about 0.1 (exp_any: 1 ulp): the reduction of exp_any with the tail l
+// and k ln2_lo folded into r = rh + e, then 1 + rh + rh^2 / 2 summed exactly (two Fast2Sums, the square's rounding error by an
+// fma) and everything below -- e (1 + rh), rh^3 (1/6 + ...) -- added as one small term before the single final rounding
+__device__ __forceinline__ double exp_hilo(double h, double l) {
+  h = fmax(h, -800.0);
+  const double k = rint(h * 1.44269504088896338700e+00);
+  const double r0 = fma(-k, 6.93147180369123816490e-01, h); // exact
+  const double rl = fma(-k, 1.90821492927058770002e-10, l);
+  const double r = r0 + rl, e = (r0 - r) + rl; // |r| <= 0.3466
+  const double zh = r * r, zl = fma(r, r, -zh);
+  double p = 1.0 / 6227020800.0;
+  p = fma(p, r, 1.0 / 479001600.0);
+  p = fma(p, r, 1.0 / 39916800.0);
+  p = fma(p, r, 1.0 / 3628800.0);
+  p = fma(p, r, 1.0 / 362880.0);
+  p = fma(p, r, 1.0 / 40320.0);
+  p = fma(p, r, 1.0 / 5040.0);
+  p = fma(p, r, 1.0 / 720.0);
+  p = fma(p, r, 1.0 / 120.0);
+  p = fma(p, r, 1.0 / 24.0);
+  p = fma(p, r, 1.0 / 6.0);
+  const double c = fma(0.5, zl, fma(zh * r, p, fma(e, r, e)));
+  const double hz = 0.5 * zh;
+  const double ah = 1.0 + r, al = (1.0 - ah) + r;
+  const double bh = ah + hz, bl = (ah - bh) + hz;
+  return ldexp(bh + ((bl + al) + c), (int)k);
+}
+// x**y for x > 0, to <= 1 ulp whatever |y ln x| is (within 0.6 ulp on T04's arguments): exp(y ln x) with ln x in two parts,
+// the product y (hi + lo) = ph + pl with the multiplication's rounding error recovered by one fma, and the exponential of the
+// pair.  x <= 0 or not finite: the library's.
+// Tested for |y ln x| up to about 250 (x in [1e-12, 1e5], y in [-1, 9]); a result that overflows or underflows double is
+// outside the domain (exp_hilo clamps its argument from below only, and (int)k leaves int for a huge one), as is y = +-inf.
 __device__ __forceinline__ double pow_pos(double x, double y) {
   if (!(x > 0.0) || !(x < 1.0e300)) return pow(x, y);
-  return exp_any(y * log_pos(x));
+  double hi, lo;
+  log_pos_hilo(x, hi, lo);
+  const double ph = y * hi;
+  return exp_hilo(ph, fma(y, lo, fma(y, hi, -ph)));
 }
 } // namespace fm
 
