@@ -57,6 +57,10 @@ def lib():
                                                      C.c_double, C.c_uint]
         L.so_model_destroy.argtypes = [C.c_void_p]
         L.so_model_set_igrf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p]
+        fp = C.POINTER(C.c_float)
+        L.so_model_get_igrf.argtypes = [C.c_void_p, fp, fp, fp, fp, dp]
+        L.so_igrf_gsw.restype = None
+        L.so_igrf_gsw.argtypes = [fp, fp, fp, fp, C.c_float, C.c_float, C.c_float, fp, fp, fp]
         L.so_model_nspec.argtypes = [C.c_void_p]
         L.so_scattered_set_spacing.argtypes = [C.c_void_p, dp, C.c_double]
         L.so_scattered_radius.restype = C.c_double
@@ -94,6 +98,24 @@ def lib():
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def igrf_gsw(G, H, REC, A, xyz):
+    """IGRF_GSW_08 of the oracle on fp32 GSW positions [n, 3] in Earth radii -> fp32 field [n, 3] in nT."""
+    G, H, REC, A = (np.ascontiguousarray(v, dtype=np.float32) for v in (G, H, REC, A))
+    assert G.size == 105 and H.size == 105 and REC.size == 105 and A.size == 9
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros_like(xyz)
+    f, o = lib().so_igrf_gsw, np.zeros(3, dtype=np.float32)
+    op = [o[i:].ctypes.data_as(C.POINTER(C.c_float)) for i in range(3)]
+    for i, (x, y, z) in enumerate(xyz):
+        f(_fp(G), _fp(H), _fp(REC), _fp(A), C.c_float(x), C.c_float(y), C.c_float(z), *op)
+        out[i] = o
+    return out
 
 
 def _ip(a):
@@ -153,6 +175,14 @@ class Model:
         if lib().so_model_set_igrf(self.h, yearday, msec, os.fsencode(path)) != 0:
             raise RuntimeError("IGRF coefficient table unreadable: %s" % path)
         return self
+
+    def igrf_state(self):
+        """After set_igrf: (G[105], H[105], REC[105], A[9]) as fp32 in geopack's order, and (cos, sin) of the dipole tilt."""
+        G, H, REC, A = (np.zeros(n, dtype=np.float32) for n in (105, 105, 105, 9))
+        cs = np.zeros(2)
+        if lib().so_model_get_igrf(self.h, _fp(G), _fp(H), _fp(REC), _fp(A), _dp(cs)) != 0:
+            raise RuntimeError("this model has no IGRF field set")
+        return G, H, REC, A, (float(cs[0]), float(cs[1]))
 
     def __del__(self):
         try:

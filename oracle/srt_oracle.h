@@ -83,6 +83,10 @@ double so_scattered_radius(const so_model *m);                              /* m
 void so_dipole_tilt(int yearday, int msec, double *mu);
 void so_bfield(so_model *m, const double x[3], double B0[3]);
 double so_speed_of_light(void);
+/* srt_oracle_igrf.c: the IGRF state of a model after so_model_set_igrf (-1 without it), and IGRF_GSW_08 itself */
+int so_model_get_igrf(const so_model *m, float G[105], float H[105], float REC[105], float A[9], double tilt_cs[2]);
+void so_igrf_gsw(const float *G, const float *H, const float *REC, const float A[9], float xgsw, float ygsw, float zgsw, float *hx,
+                 float *hy, float *hz);
 
 #ifdef __cplusplus
 }

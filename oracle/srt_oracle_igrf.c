@@ -258,3 +258,16 @@ int so_model_set_igrf(so_model *m, int yearday, int msec, const char *coeff_file
   free(t);
   return 0;
 }
+
+/* test accessor: what so_model_set_igrf left in the model (G, H, REC in geopack's index n(n-1)/2 + m, A row-major) and
+ * cos / sin of the model's dipole tilt mu; returns -1 when the model has no IGRF set */
+int so_model_get_igrf(const so_model *m, float G[105], float H[105], float REC[105], float A[9], double tilt_cs[2]) {
+  if (!m || !m->use_igrf) return -1;
+  memcpy(G, m->igrf_G, sizeof m->igrf_G);
+  memcpy(H, m->igrf_H, sizeof m->igrf_H);
+  memcpy(REC, m->igrf_REC, sizeof m->igrf_REC);
+  memcpy(A, m->igrf_A, sizeof m->igrf_A);
+  tilt_cs[0] = cos(m->mu);
+  tilt_cs[1] = sin(m->mu);
+  return 0;
+}

@@ -345,13 +345,7 @@ extern "C" int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenk
     std::string err;
     float G[105], H[105], REC[105];
     if (!srt_host::igrf_setup(path.c_str(), f.yearday, f.msec, G, H, REC, f.A, &f.psi, err)) return srt_set_error(SRT_EIO, "%s", err.c_str());
-    for (int mm = 1; mm <= 14; ++mm)
-      for (int n = mm; n <= 14; ++n) { // geopack's index n(n-1)/2 + m  ->  visiting order
-        const int mn = n * (n - 1) / 2 + mm - 1, e = igrf_off(mm) + n - mm;
-        f.Gv[e] = G[mn];
-        f.Hv[e] = H[mn];
-        f.Rv[e] = REC[mn];
-      }
+    igrf_pack_terms(G, H, REC, f);
   }
   f.use_igrf = use_igrf;
   f.use_tsy = use_tsyganenko;

@@ -50,6 +50,16 @@ struct FieldConst {
 };
 // (rows m >= 6 start at 64: no row straddles the two register halves, so the half is chosen once per m, not per term)
 __host__ __device__ inline int igrf_off(int m) { return (m - 1) * 15 - (m - 1) * m / 2 + (m >= 6 ? 4 : 0); }
+// host: G, H, REC in geopack's index n(n-1)/2 + m (srt_host::igrf_setup)  ->  the visiting order above
+inline void igrf_pack_terms(const float G[105], const float H[105], const float REC[105], FieldConst &f) {
+  for (int mm = 1; mm <= 14; ++mm)
+    for (int n = mm; n <= 14; ++n) {
+      const int mn = n * (n - 1) / 2 + mm - 1, e = igrf_off(mm) + n - mm;
+      f.Gv[e] = G[mn];
+      f.Hv[e] = H[mn];
+      f.Rv[e] = REC[mn];
+    }
+}
 
 struct Common {
   Species sp;

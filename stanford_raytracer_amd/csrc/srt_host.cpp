@@ -102,7 +102,16 @@ bool igrf_setup(const char *coeff_file, int yearday, int msec, float G[105], flo
     char *s = line + 1;
     const long mn = strtol(s, &s, 10);
     if (mn < 1 || mn > 105) continue;
-    for (int e = 0; e <= NEP; ++e) (line[0] == 'g' ? tg : th)[e * 105 + (mn - 1)] = strtof(s, &s);
+    for (int e = 0; e <= NEP; ++e) {
+      char *end = s;
+      (line[0] == 'g' ? tg : th)[e * 105 + (mn - 1)] = strtof(s, &end);
+      if (end == s) { // a row cut short (a truncated file): never a silent zero
+        fclose(f);
+        err = std::string("IGRF coefficient table has a row with fewer than 13 values: ") + coeff_file;
+        return false;
+      }
+      s = end;
+    }
     ++seen;
   }
   fclose(f);
