@@ -3,12 +3,19 @@
 // There is no CPU fallback: every entry point fails with SRT_EDEVICE when no GPU is usable.
 #include <hip/hip_runtime.h>
 
+#include <dlfcn.h>
+
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/srt.h"
@@ -45,12 +52,54 @@ extern "C" const char *srt_last_error(void) { return g_err.c_str(); }
                            hipGetErrorString(e_));                                            \
   } while (0)
 
+// The one owner of device memory in this file: an array of T that frees itself.  alloc() is exact and drops what was held first;
+// reserve() only ever grows, with room to spare, and keeps the first `keep` elements (the sampler's pools).
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t cap = 0; // elements
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  hipError_t alloc(size_t n) {
+    release();
+    const hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e == hipSuccess) cap = n;
+    else p = nullptr;
+    return e;
+  }
+  int reserve(size_t n, size_t keep = 0) {
+    if (n <= cap) return 0;
+    const size_t want = n + n / 2 + 4096;
+    T *q = nullptr;
+    if (hipMalloc(&q, want * sizeof(T)) != hipSuccess) return -1;
+    if (p && keep && hipMemcpy(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
+      (void)hipFree(q);
+      return -1;
+    }
+    release();
+    p = q;
+    cap = want;
+    return 0;
+  }
+  void swap(DevBuf &o) {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+  }
+  template <class U> U *as() const { return (U *)p; }
+};
+using DevBytes = DevBuf<char>;
+
 // Device selection.  srt_init(device) binds the CALLING THREAD to a device (and makes it the process default for
 // threads that never called srt_init): one host thread per GPU may drive its own models concurrently (the CLI's
 // --devices=0,1,..).  A model remembers the device it was created on, and every entry point that takes a model
 // switches to that device first, whichever thread calls it.
-#include <atomic>
-#include <mutex>
 static std::atomic<int> g_default_device{-1};
 static thread_local int t_device = -1;
 extern "C" int srt_init(int device) {
@@ -131,23 +180,28 @@ extern "C" int srt_device_info(char *name, int name_len, int *cu_count, int64_t 
 }
 
 // ------------------------------------------------------------------------------------------ model
+enum ModelKind { KIND_NGO = 1, KIND_INTERP = 3, KIND_SCATTERED = 4, KIND_NGO3D = 5, KIND_SIMPLE3D = 6 }; // the driver's modelnum
+
 struct srt_model {
   int kind = 0, nspec = 0;
   int device = current_device(); // the HIP device the tables live on (the creating thread's)
   Common cm{};
-  NgoModel ngo{};
-  InterpModel interp{};
-  ScatteredModel scat{};
-  Simple3dModel s3{};
-  Ngo3dModel ngo3{};
-  double *d_pts = nullptr;
-  double *d_xyz = nullptr; // scattered model: the sample positions once more, SoA [3][npts] (the candidate scans read only these)
-  int *d_cells = nullptr;
-  double *d_coef = nullptr;
-  void *d_model = nullptr;   // device copy of ngo / interp (kernels read it through scalar loads)
-  Common *d_common = nullptr;
+  std::tuple<NgoModel, InterpModel, ScatteredModel, Ngo3dModel, Simple3dModel> host{}; // the host copy of `kind`'s struct
+  template <class M> M &as() { return std::get<M>(host); }
+  DevBuf<double> d_pts;
+  DevBuf<double> d_xyz; // scattered model: the sample positions once more, SoA [3][npts] (the candidate scans read only these)
+  DevBuf<int> d_cells;
+  DevBuf<double> d_coef;
+  DevBytes d_model; // device copy of the host struct (kernels read it through scalar loads)
+  template <class M> const M *on_device() const { return (const M *)d_model.p; }
+  DevBuf<Common> d_common;
   int64_t device_bytes = 0;
   int cu_count = 256;
+  // scattered model (grow-only): scratch for the one-wave blocks of a launch, so many doubles per block
+  struct Scratch {
+    DevBuf<double> buf;
+    long long blocks = 0, failed = 0; // (failed: the grid size whose allocation was refused -- not retried per launch)
+  };
   // Per-launch scratch in NSLOT slots, so that launches on different streams may overlap.  A launch takes a slot whose previous
   // launch has FINISHED (its `done` event has fired) before it opens a new one: a caller that launches from one stream, one
   // launch after the other, lives in a single slot (scattered model: 9.7 GB of candidate blocks + staging per slot at grid 2048),
@@ -156,16 +210,22 @@ struct srt_model {
     hipEvent_t done = nullptr; // recorded behind the launch that used this slot's scratch last
     bool used = false;
     // ray_order option (grow-only): keys in/out, ids in/out, radix-sort workspace
-    unsigned *d_keys[2] = {nullptr, nullptr};
-    int *d_ids[2] = {nullptr, nullptr};
-    void *d_sorttmp = nullptr;
-    size_t sort_cap = 0, sorttmp_bytes = 0;
-    // scattered model (grow-only): staging records of coop_stencil, REC_CAP * REC doubles per one-wave block
-    double *d_stage = nullptr;
-    long long stage_blocks = 0, stage_failed = 0; // (failed: the grid size whose allocation was refused -- not retried per launch)
-    // scattered model (grow-only): the lanes' candidate blocks, BLOCK_DOUBLES per one-wave block
-    double *d_blocks = nullptr;
-    long long cand_blocks = 0, cand_failed = 0;
+    DevBuf<unsigned> keys[2];
+    DevBuf<int> ids[2];
+    DevBytes sorttmp;
+    Scratch stage; // staging records of coop_stencil, REC_CAP * REC doubles per block
+    Scratch cand;  // the lanes' candidate blocks, BLOCK_DOUBLES per block
+    // frees the scratch and forgets refused sizes; the caller has waited for `done` where a launch may still read it
+    void release() {
+      for (int k = 0; k < 2; ++k) {
+        keys[k].release();
+        ids[k].release();
+      }
+      sorttmp.release();
+      stage.buf.release();
+      cand.buf.release();
+      stage.blocks = stage.failed = cand.blocks = cand.failed = 0;
+    }
   };
   static constexpr int NSLOT = 4;
   LaunchSlot slot[NSLOT];
@@ -182,24 +242,49 @@ struct srt_model {
   // device staging of the host-buffer entry point srt_trace_batch (grow-only, freed with the model): the CLI calls it
   // once per chunk of the ray file, and a fresh hipMalloc / hipFree of gigabytes per call costs as much as a small launch
   struct HostIO {
-    void *p[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t cap[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    DevBytes buf[9];
+    void release() {
+      for (auto &b : buf) b.release();
+    }
   } io;
   std::mutex io_lock; // one srt_trace_batch (host-buffer call) per model at a time: the staging above is shared
 };
 static int io_reserve(srt_model *m, int k, size_t bytes, void **out) {
-  if (bytes > m->io.cap[k]) {
-    if (m->io.p[k]) (void)hipFree(m->io.p[k]);
-    m->io.p[k] = nullptr;
-    m->io.cap[k] = 0;
-    if (hipMalloc(&m->io.p[k], bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return srt_set_error(SRT_ENOMEM, "hipMalloc of %zu bytes failed", bytes);
-    }
-    m->io.cap[k] = bytes;
+  DevBytes &b = m->io.buf[k];
+  if (bytes > b.cap && b.alloc(bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return srt_set_error(SRT_ENOMEM, "hipMalloc of %zu bytes failed", bytes);
   }
-  *out = m->io.p[k];
+  *out = b.p;
   return SRT_OK;
+}
+
+template <class K, class... Args>
+static void launch_wave_blocks(K kernel, long long n, hipStream_t st, Args... args) {
+  long long blocks = (n + WAVE - 1) / WAVE;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), 0, st, args...);
+}
+
+// The one place that turns a kind number into a type: f is a generic callable and gets a ModelTag -- the model's struct, whether
+// its lookups use the wave's LDS tile, and how many one-wave blocks per CU the persistent grid of its trace launch has (interp:
+// 34 KiB of LDS per wave, 512 registers per lane: one wave per SIMD; scattered: 18.5 KiB, <= 256 registers: WAVES_PER_EU per
+// SIMD; ngo3d and simple3d: as Ngo, whose integrator fills the default WaveBudget whatever the density body needs).
+template <class M, bool LDS, int WAVES_PER_CU>
+struct ModelTag {
+  using Model = M;
+  static constexpr bool lds = LDS;
+  static constexpr int waves_per_cu = WAVES_PER_CU;
+};
+template <class F>
+static int with_model(const srt_model *m, F &&f) {
+  switch (m->kind) {
+  case KIND_NGO: return f(ModelTag<NgoModel, false, 8>{});
+  case KIND_INTERP: return f(ModelTag<InterpModel, true, 4>{});
+  case KIND_SCATTERED: return f(ModelTag<ScatteredModel, true, 4 * ScatteredModel::WAVES_PER_EU>{});
+  case KIND_NGO3D: return f(ModelTag<Ngo3dModel, false, 8>{});
+  case KIND_SIMPLE3D: return f(ModelTag<Simple3dModel, false, 8>{});
+  }
+  return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
 }
 
 // switch the calling thread to the model's device until the enclosing entry point returns
@@ -231,24 +316,15 @@ static void fill_common(Common &cm, int nspec, const double *qs, const double *m
 }
 
 static int model_finish(srt_model *m) {
-  HIP_OK(hipMalloc(&m->d_common, sizeof(Common)));
-  HIP_OK(hipMemcpy(m->d_common, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
-  if (m->kind == 1) {
-    HIP_OK(hipMalloc(&m->d_model, sizeof(NgoModel)));
-    HIP_OK(hipMemcpy(m->d_model, &m->ngo, sizeof(NgoModel), hipMemcpyHostToDevice));
-  } else if (m->kind == 3) {
-    HIP_OK(hipMalloc(&m->d_model, sizeof(InterpModel)));
-    HIP_OK(hipMemcpy(m->d_model, &m->interp, sizeof(InterpModel), hipMemcpyHostToDevice));
-  } else if (m->kind == 4) {
-    HIP_OK(hipMalloc(&m->d_model, sizeof(ScatteredModel)));
-    HIP_OK(hipMemcpy(m->d_model, &m->scat, sizeof(ScatteredModel), hipMemcpyHostToDevice));
-  } else if (m->kind == 5) {
-    HIP_OK(hipMalloc(&m->d_model, sizeof(Ngo3dModel)));
-    HIP_OK(hipMemcpy(m->d_model, &m->ngo3, sizeof(Ngo3dModel), hipMemcpyHostToDevice));
-  } else if (m->kind == 6) {
-    HIP_OK(hipMalloc(&m->d_model, sizeof(Simple3dModel)));
-    HIP_OK(hipMemcpy(m->d_model, &m->s3, sizeof(Simple3dModel), hipMemcpyHostToDevice));
-  }
+  HIP_OK(m->d_common.alloc(1));
+  HIP_OK(hipMemcpy(m->d_common.p, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
+  int rc = with_model(m, [&](auto tag) -> int {
+    using M = typename decltype(tag)::Model;
+    HIP_OK(m->d_model.alloc(sizeof(M)));
+    HIP_OK(hipMemcpy(m->d_model.p, &m->as<M>(), sizeof(M), hipMemcpyHostToDevice));
+    return SRT_OK;
+  });
+  if (rc) return rc;
   hipDeviceProp_t p;
   m->device = current_device();
   HIP_OK(hipGetDeviceProperties(&p, m->device));
@@ -265,29 +341,16 @@ extern "C" void srt_model_destroy(srt_model *m) {
   if (!m) return;
   SRT_MODEL_SCOPE; // its tables and events live on m->device; the caller's device is back when this returns
   (void)ensure_model(m);
-  if (m->d_coef) (void)hipFree(m->d_coef);
-  if (m->d_pts) (void)hipFree(m->d_pts);
-  if (m->d_xyz) (void)hipFree(m->d_xyz);
-  if (m->d_cells) (void)hipFree(m->d_cells);
-  if (m->d_model) (void)hipFree(m->d_model);
   for (auto &sl : m->slot) {
-    for (int k = 0; k < 2; ++k) {
-      if (sl.d_keys[k]) (void)hipFree(sl.d_keys[k]);
-      if (sl.d_ids[k]) (void)hipFree(sl.d_ids[k]);
-    }
-    if (sl.d_sorttmp) (void)hipFree(sl.d_sorttmp);
-    if (sl.d_stage) (void)hipFree(sl.d_stage);
-    if (sl.d_blocks) (void)hipFree(sl.d_blocks);
+    sl.release();
     if (sl.done) (void)hipEventDestroy(sl.done);
   }
   for (auto &h : m->hist) {
     if (h.ev0) (void)hipEventDestroy(h.ev0);
     if (h.ev1) (void)hipEventDestroy(h.ev1);
   }
-  if (m->d_common) (void)hipFree(m->d_common);
-  for (void *q : m->io.p)
-    if (q) (void)hipFree(q);
-  delete m;
+  m->io.release();
+  delete m; // the tables free themselves
 }
 extern "C" int srt_model_trim(srt_model *m) {
   if (!m) return srt_set_error(SRT_EINVAL, "null model");
@@ -297,31 +360,12 @@ extern "C" int srt_model_trim(srt_model *m) {
   std::lock_guard<std::mutex> hold(m->io_lock);
   for (auto &sl : m->slot) {
     if (sl.used) HIP_OK(hipEventSynchronize(sl.done)); // the launch that used this slot's scratch is over
-    for (int k = 0; k < 2; ++k) {
-      if (sl.d_keys[k]) (void)hipFree(sl.d_keys[k]);
-      if (sl.d_ids[k]) (void)hipFree(sl.d_ids[k]);
-      sl.d_keys[k] = nullptr;
-      sl.d_ids[k] = nullptr;
-    }
-    if (sl.d_sorttmp) (void)hipFree(sl.d_sorttmp);
-    if (sl.d_stage) (void)hipFree(sl.d_stage);
-    if (sl.d_blocks) (void)hipFree(sl.d_blocks);
-    sl.d_sorttmp = nullptr;
-    sl.d_stage = nullptr;
-    sl.d_blocks = nullptr;
-    sl.sort_cap = sl.sorttmp_bytes = 0;
-    sl.stage_blocks = sl.cand_blocks = 0;
-    sl.stage_failed = sl.cand_failed = 0;
+    sl.release();
   }
-  for (int k = 0; k < 9; ++k) {
-    if (m->io.p[k]) (void)hipFree(m->io.p[k]);
-    m->io.p[k] = nullptr;
-    m->io.cap[k] = 0;
-  }
+  m->io.release();
   return SRT_OK;
 }
 // use_igrf (raytracer_driver.f95 --use_igrf; interp_dens_model_adapter.f95:236-241 and twins)
-#include <dlfcn.h>
 extern "C" int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenko, const char *igrf_coeff_file) {
   if (!m) return srt_set_error(SRT_EINVAL, "null model");
   if (use_tsyganenko != 0 && use_tsyganenko != 1) return srt_set_error(SRT_EINVAL, "use_tsyganenko must be 0 or 1");
@@ -349,7 +393,7 @@ extern "C" int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenk
   }
   f.use_igrf = use_igrf;
   f.use_tsy = use_tsyganenko;
-  HIP_OK(hipMemcpy(m->d_common, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(m->d_common.p, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
   return SRT_OK;
 }
 // T04_s's PARMOD (driver flags --tsyganenko_Pdyn, _Dst, _ByIMF, _BzIMF, _W1 .. _W6; raytracer_driver.f95:292-341)
@@ -359,7 +403,7 @@ extern "C" int srt_model_set_tsyganenko_params(srt_model *m, const double parmod
   int rc = ensure_model(m);
   if (rc) return rc;
   for (int i = 0; i < 10; ++i) m->cm.fld.parmod[i] = (float)parmod[i]; // real(parmod)
-  HIP_OK(hipMemcpy(m->d_common, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(m->d_common.p, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
   return SRT_OK;
 }
 extern "C" int srt_model_kind(const srt_model *m) { return m ? m->kind : 0; }
@@ -389,12 +433,11 @@ static int ngo_readinput(const char *configfile, NgoModel &g) {
   ngo_fill(cfg, g);
   double z1, sinz22;
   ngo_norm_point(cfg, g, z1, sinz22);
-  double *d_out = nullptr;
+  DevBuf<double> d_out;
   double ani1 = 0.0;
-  if (hipMalloc(&d_out, sizeof(double)) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-  hipLaunchKernelGGL(ngo_norm_kernel, dim3(1), dim3(1), 0, 0, g, z1, sinz22, cfg.last_latitu, d_out);
-  hipError_t e = hipMemcpy(&ani1, d_out, sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d_out);
+  if (d_out.alloc(1) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  hipLaunchKernelGGL(ngo_norm_kernel, dim3(1), dim3(1), 0, 0, g, z1, sinz22, cfg.last_latitu, d_out.p);
+  hipError_t e = hipMemcpy(&ani1, d_out.p, sizeof(double), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "ngo normalisation kernel failed: %s", hipGetErrorString(e));
   g.ane0 = g.ane0 * cfg.dsdens / ani1;
   return SRT_OK;
@@ -422,9 +465,9 @@ extern "C" int srt_model_create_ngo(const char *configfile, int yearday, int mse
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
   srt_model *m = new srt_model;
-  m->kind = 1;
+  m->kind = KIND_NGO;
   m->nspec = 4;
-  rc = ngo_readinput(configfile, m->ngo);
+  rc = ngo_readinput(configfile, m->as<NgoModel>());
   if (rc) {
     delete m;
     return rc;
@@ -442,16 +485,17 @@ extern "C" int srt_model_create_ngo3d(const char *configfile, double kp, int fix
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
   srt_model *m = new srt_model;
-  m->kind = 5;
+  m->kind = KIND_NGO3D;
   m->nspec = 4;
-  rc = ngo_readinput(configfile, m->ngo3.ngo); // ane0 is normalised with the file's lk (readinput runs once, at setup)
+  Ngo3dModel &g = m->as<Ngo3dModel>();
+  rc = ngo_readinput(configfile, g.ngo); // ane0 is normalised with the file's lk (readinput runs once, at setup)
   if (rc) {
     delete m;
     return rc;
   }
-  m->ngo3.kp = kp;
-  m->ngo3.fixed_mlt = fixed_MLT;
-  m->ngo3.mlt = MLT;
+  g.kp = kp;
+  g.fixed_mlt = fixed_MLT;
+  g.mlt = MLT;
   return ngo_finish(m, yearday, msec, out);
 }
 
@@ -464,13 +508,14 @@ extern "C" int srt_model_create_simple3d(double kp, int fixed_MLT, double MLT, i
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
   srt_model *m = new srt_model;
-  m->kind = 6;
+  m->kind = KIND_SIMPLE3D;
   m->nspec = 4;
-  m->s3.c.kp = kp;
-  m->s3.c.year = yearday / 1000; // iyear = itime(1)/1000, doy = itime(1) - iyear*1000 (:743-744)
-  m->s3.c.doy = yearday - m->s3.c.year * 1000;
-  m->s3.c.fixed_mlt = fixed_MLT;
-  m->s3.c.mlt = MLT;
+  auto &c = m->as<Simple3dModel>().c;
+  c.kp = kp;
+  c.year = yearday / 1000; // iyear = itime(1)/1000, doy = itime(1) - iyear*1000 (:743-744)
+  c.doy = yearday - c.year * 1000;
+  c.fixed_mlt = fixed_MLT;
+  c.mlt = MLT;
   // the adapter's own species constants (:813-815)
   const double e_ = 1.602e-19;
   double qs[4] = {e_ * -1.0, e_, e_, e_};
@@ -575,9 +620,10 @@ __global__ __launch_bounds__(64) void build_coeffs_kernel(GridDims g, ArrPtrs ar
 }
 
 // FD derivatives (unless given) + coefficient expansion + model object, from the 8 arrays already on the device.
-// d_arr[0] = F; d_arr[1..7] = derivative blocks (contents ignored when !have_derivs).  The arrays are freed here.
+// arr[0] = F; arr[1..7] = derivative blocks (contents ignored when !have_derivs).  The arrays are freed here, before the model
+// is made.
 static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const double bounds[6], const double *qs,
-                                     const double *ms, double *d_arr[8], bool have_derivs, int yearday, int msec,
+                                     const double *ms, DevBuf<double> (&arr)[8], bool have_derivs, int yearday, int msec,
                                      srt_model **out) {
   const size_t nnode = (size_t)nx * ny * nz, n = nnode * nspec;
   const size_t ncell = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
@@ -586,20 +632,13 @@ static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const do
   double dx = (bounds[1] - bounds[0]) / (nx - 1.0);
   double dy = (bounds[3] - bounds[2]) / (ny - 1.0);
   double dz = (bounds[5] - bounds[4]) / (nz - 1.0);
-  double *d_coef = nullptr;
-  auto cleanup = [&]() {
-    for (int a = 0; a < 8; ++a)
-      if (d_arr[a]) {
-        (void)hipFree(d_arr[a]);
-        d_arr[a] = nullptr;
-      }
-  };
+  DevBuf<double> coef;
   hipError_t e = hipSuccess;
   if (!have_derivs) {
-    for (int a = 1; a < 8 && e == hipSuccess; ++a) e = hipMemset(d_arr[a], 0, n * sizeof(double));
+    for (int a = 1; a < 8 && e == hipSuccess; ++a) e = hipMemset(arr[a].p, 0, n * sizeof(double));
     int blocks = (int)((n + 255) / 256 < 65535 * 4 ? (n + 255) / 256 : 65535 * 4);
     auto fd = [&](int src, int dst, int axis, double h) {
-      hipLaunchKernelGGL(fd_axis_kernel, dim3(blocks), dim3(256), 0, 0, g, (const double *)d_arr[src], d_arr[dst], axis, h);
+      hipLaunchKernelGGL(fd_axis_kernel, dim3(blocks), dim3(256), 0, 0, g, (const double *)arr[src].p, arr[dst].p, axis, h);
     };
     // order and guards of libtricubic.f95:736-790
     if (nx > 2) fd(0, 1, 0, dx);
@@ -610,35 +649,31 @@ static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const do
     if (ny > 2 && nz > 2) fd(3, 6, 1, dy);
     if (nx > 2 && ny > 2 && nz > 2) fd(6, 7, 0, dx);
   }
-  if (e == hipSuccess) e = hipMalloc(&d_coef, ncell * nspec * 64 * sizeof(double));
-  if (e != hipSuccess) {
-    cleanup();
+  if (e == hipSuccess) e = coef.alloc(ncell * nspec * 64);
+  if (e != hipSuccess)
     return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "interp model setup: %s", hipGetErrorString(e));
-  }
   (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_ptr), TRI_PTR, sizeof TRI_PTR);
   (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_col), TRI_COL, sizeof TRI_COL);
   (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_val), TRI_VAL, sizeof TRI_VAL);
   ArrPtrs ap;
-  for (int a = 0; a < 8; ++a) ap.a[a] = d_arr[a];
+  for (int a = 0; a < 8; ++a) ap.a[a] = arr[a].p;
   long long npairs = (long long)ncell * nspec;
   int blocks = (int)(npairs < 262144 ? npairs : 262144);
-  hipLaunchKernelGGL(build_coeffs_kernel, dim3(blocks), dim3(64), 0, 0, g, ap, dx, dy, dz, d_coef, npairs);
+  hipLaunchKernelGGL(build_coeffs_kernel, dim3(blocks), dim3(64), 0, 0, g, ap, dx, dy, dz, coef.p, npairs);
   e = hipDeviceSynchronize();
-  cleanup();
-  if (e != hipSuccess) {
-    (void)hipFree(d_coef);
-    return srt_set_error(SRT_EDEVICE, "coefficient build failed: %s", hipGetErrorString(e));
-  }
+  for (auto &b : arr) b.release();
+  if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "coefficient build failed: %s", hipGetErrorString(e));
   srt_model *m = new srt_model;
-  m->kind = 3;
+  m->kind = KIND_INTERP;
   m->nspec = nspec;
-  m->d_coef = d_coef;
+  m->d_coef.swap(coef);
   m->device_bytes = (int64_t)(ncell * nspec * 64 * sizeof(double));
-  m->interp.coef = d_coef;
-  m->interp.nspec = nspec;
-  m->interp.ax = Axis{bounds[0], dx, 1.0 / dx, nx};
-  m->interp.ay = Axis{bounds[2], dy, 1.0 / dy, ny};
-  m->interp.az = Axis{bounds[4], dz, 1.0 / dz, nz};
+  InterpModel &im = m->as<InterpModel>();
+  im.coef = m->d_coef.p;
+  im.nspec = nspec;
+  im.ax = Axis{bounds[0], dx, 1.0 / dx, nx};
+  im.ay = Axis{bounds[2], dy, 1.0 / dy, ny};
+  im.az = Axis{bounds[4], dz, 1.0 / dz, nz};
   fill_common(m->cm, nspec, qs, ms, yearday, msec);
   int rc = model_finish(m);
   if (rc) {
@@ -649,14 +684,10 @@ static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const do
   return SRT_OK;
 }
 
-static int alloc_grid_arrays(size_t n, double *d_arr[8]) {
-  for (int a = 0; a < 8; ++a) d_arr[a] = nullptr;
-  for (int a = 0; a < 8; ++a) {
-    if (hipMalloc(&d_arr[a], n * sizeof(double)) != hipSuccess) {
-      for (int b = 0; b < a; ++b) (void)hipFree(d_arr[b]);
+static int alloc_grid_arrays(size_t n, DevBuf<double> (&arr)[8]) {
+  for (auto &b : arr)
+    if (b.alloc(n) != hipSuccess)
       return srt_set_error(SRT_ENOMEM, "hipMalloc of grid arrays failed (%zu bytes each)", n * sizeof(double));
-    }
-  }
   return SRT_OK;
 }
 
@@ -672,18 +703,15 @@ extern "C" int srt_model_create_interp(int nspec, int nx, int ny, int nz, const 
   if (rc) return rc;
   const size_t n = (size_t)nx * ny * nz * nspec;
   if ((size_t)(nx + 1) * (ny + 1) * (nz + 1) >= (size_t)1 << 31) return srt_set_error(SRT_EINVAL, "grid too large");
-  double *d_arr[8];
-  rc = alloc_grid_arrays(n, d_arr);
+  DevBuf<double> arr[8];
+  rc = alloc_grid_arrays(n, arr);
   if (rc) return rc;
-  hipError_t e = hipMemcpy(d_arr[0], F, n * sizeof(double), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpy(arr[0].p, F, n * sizeof(double), hipMemcpyHostToDevice);
   if (derivs)
     for (int a = 1; a < 8 && e == hipSuccess; ++a)
-      e = hipMemcpy(d_arr[a], derivs[a - 1], n * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    for (int a = 0; a < 8; ++a) (void)hipFree(d_arr[a]);
-    return srt_set_error(SRT_EDEVICE, "grid upload: %s", hipGetErrorString(e));
-  }
-  return interp_from_device_arrays(nspec, nx, ny, nz, bounds, qs, ms, d_arr, derivs != nullptr, yearday, msec, out);
+      e = hipMemcpy(arr[a].p, derivs[a - 1], n * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "grid upload: %s", hipGetErrorString(e));
+  return interp_from_device_arrays(nspec, nx, ny, nz, bounds, qs, ms, arr, derivs != nullptr, yearday, msec, out);
 }
 
 // ---- the step before the path: sample a model on a regular grid, in log space, on the device ----
@@ -775,9 +803,9 @@ __global__ __launch_bounds__(64) void sample_grid_kernel(const M *__restrict__ m
   }
 }
 
-// fills d_arr[0] (and d_arr[1..7] when compder) on the device
+// fills arr[0] (and arr[1..7] when compder) on the device
 static int sample_model_on_grid(srt_model *src, int compder, int nx, int ny, int nz, const double bounds[6],
-                                double *d_arr[8]) {
+                                DevBuf<double> (&arr)[8]) {
   GridDims g{src->nspec, nx, ny, nz};
   SampleArgs A;
   // gcpm_dens_model_buildgrid.f95:161-163
@@ -787,20 +815,15 @@ static int sample_model_on_grid(srt_model *src, int compder, int nx, int ny, int
   A.min[0] = bounds[0];
   A.min[1] = bounds[2];
   A.min[2] = bounds[4];
-  for (int a = 0; a < 8; ++a) A.a[a] = d_arr[a];
+  for (int a = 0; a < 8; ++a) A.a[a] = arr[a].p;
   A.nnode = (long long)nx * ny * nz;
   A.compder = compder;
-  const unsigned blocks = (unsigned)((A.nnode + WAVE - 1) / WAVE);
-  if (src->kind == 1)
-    hipLaunchKernelGGL((sample_grid_kernel<NgoModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const NgoModel *)src->d_model, g, A);
-  else if (src->kind == 3)
-    hipLaunchKernelGGL((sample_grid_kernel<InterpModel, true>), dim3(blocks), dim3(WAVE), 0, 0, (const InterpModel *)src->d_model, g, A);
-  else if (src->kind == 5)
-    hipLaunchKernelGGL((sample_grid_kernel<Ngo3dModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const Ngo3dModel *)src->d_model, g, A);
-  else if (src->kind == 6)
-    hipLaunchKernelGGL((sample_grid_kernel<Simple3dModel, false>), dim3(blocks), dim3(WAVE), 0, 0, (const Simple3dModel *)src->d_model, g, A);
-  else
-    hipLaunchKernelGGL((sample_grid_kernel<ScatteredModel, true>), dim3(blocks), dim3(WAVE), 0, 0, (const ScatteredModel *)src->d_model, g, A);
+  const int rc = with_model(src, [&](auto tag) -> int {
+    using T = decltype(tag);
+    launch_wave_blocks(sample_grid_kernel<typename T::Model, T::lds>, A.nnode, 0, src->on_device<typename T::Model>(), g, A);
+    return SRT_OK;
+  });
+  if (rc) return rc;
   hipError_t e = hipDeviceSynchronize();
   if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "grid sampling failed: %s", hipGetErrorString(e));
   return SRT_OK;
@@ -822,19 +845,12 @@ extern "C" int srt_build_grid(srt_model *src, int compder, int nx, int ny, int n
   if ((rc = ensure_model(src))) return rc;
   if (!F || (compder && !derivs)) return srt_set_error(SRT_EINVAL, "null output");
   const size_t n = (size_t)nx * ny * nz * src->nspec;
-  double *d_arr[8];
-  rc = alloc_grid_arrays(n, d_arr);
-  if (rc) return rc;
-  rc = sample_model_on_grid(src, compder ? 1 : 0, nx, ny, nz, bounds, d_arr);
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipMemcpy(F, d_arr[0], n * sizeof(double), hipMemcpyDeviceToHost);
-    if (compder)
-      for (int a = 1; a < 8 && e == hipSuccess; ++a)
-        e = hipMemcpy(derivs + (size_t)(a - 1) * n, d_arr[a], n * sizeof(double), hipMemcpyDeviceToHost);
-  }
-  for (int a = 0; a < 8; ++a) (void)hipFree(d_arr[a]);
-  if (rc) return rc;
+  DevBuf<double> arr[8];
+  if ((rc = alloc_grid_arrays(n, arr)) || (rc = sample_model_on_grid(src, compder ? 1 : 0, nx, ny, nz, bounds, arr))) return rc;
+  hipError_t e = hipMemcpy(F, arr[0].p, n * sizeof(double), hipMemcpyDeviceToHost);
+  if (compder)
+    for (int a = 1; a < 8 && e == hipSuccess; ++a)
+      e = hipMemcpy(derivs + (size_t)(a - 1) * n, arr[a].p, n * sizeof(double), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "grid download: %s", hipGetErrorString(e));
   return SRT_OK;
 }
@@ -847,15 +863,9 @@ extern "C" int srt_model_create_interp_from_model(srt_model *src, int compder, i
   SRT_MODEL_SCOPE; // the new model is built beside its source, on the source's device
   if ((rc = ensure_model(src))) return rc;
   const size_t n = (size_t)nx * ny * nz * src->nspec;
-  double *d_arr[8];
-  rc = alloc_grid_arrays(n, d_arr);
-  if (rc) return rc;
-  rc = sample_model_on_grid(src, compder ? 1 : 0, nx, ny, nz, bounds, d_arr);
-  if (rc) {
-    for (int a = 0; a < 8; ++a) (void)hipFree(d_arr[a]);
-    return rc;
-  }
-  return interp_from_device_arrays(src->nspec, nx, ny, nz, bounds, src->cm.sp.q, src->cm.sp.m, d_arr, compder != 0,
+  DevBuf<double> arr[8];
+  if ((rc = alloc_grid_arrays(n, arr)) || (rc = sample_model_on_grid(src, compder ? 1 : 0, nx, ny, nz, bounds, arr))) return rc;
+  return interp_from_device_arrays(src->nspec, nx, ny, nz, bounds, src->cm.sp.q, src->cm.sp.m, arr, compder != 0,
                                    yearday, msec, out);
 }
 
@@ -901,26 +911,26 @@ extern "C" int srt_model_create_scattered_file_root(const char *ptsfile, int yea
   if (!srt_host::build_scattered(ptsfile, window_scale, h, err, 1.0 + bmargin, (long long)root_sample))
     return srt_set_error(SRT_EIO, "%s: %s", ptsfile, err.c_str());
   srt_model *m = new srt_model;
-  m->kind = 4;
+  m->kind = KIND_SCATTERED;
   m->nspec = h.nspec;
   std::vector<double> xyz(3 * (size_t)h.npts);
   for (size_t i = 0; i < (size_t)h.npts; ++i)
     for (int c = 0; c < 3; ++c) xyz[(size_t)c * h.npts + i] = h.pts[8 * i + c];
-  hipError_t e = hipMalloc(&m->d_pts, h.pts.size() * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&m->d_cells, h.cell_start.size() * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&m->d_xyz, xyz.size() * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(m->d_xyz, xyz.data(), xyz.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(m->d_pts, h.pts.data(), h.pts.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(m->d_cells, h.cell_start.data(), h.cell_start.size() * sizeof(int), hipMemcpyHostToDevice);
+  hipError_t e = m->d_pts.alloc(h.pts.size());
+  if (e == hipSuccess) e = m->d_cells.alloc(h.cell_start.size());
+  if (e == hipSuccess) e = m->d_xyz.alloc(xyz.size());
+  if (e == hipSuccess) e = hipMemcpy(m->d_xyz.p, xyz.data(), xyz.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->d_pts.p, h.pts.data(), h.pts.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(m->d_cells.p, h.cell_start.data(), h.cell_start.size() * sizeof(int), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     srt_model_destroy(m);
     return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "scattered model upload: %s", hipGetErrorString(e));
   }
   m->device_bytes = (int64_t)((h.pts.size() + xyz.size()) * sizeof(double) + h.cell_start.size() * sizeof(int));
-  ScatteredModel &s = m->scat;
-  s.pts = m->d_pts;
-  s.xyz = m->d_xyz;
-  s.cell_start = m->d_cells;
+  ScatteredModel &s = m->as<ScatteredModel>();
+  s.pts = m->d_pts.p;
+  s.xyz = m->d_xyz.p;
+  s.cell_start = m->d_cells.p;
   for (int k = 0; k < 3; ++k) {
     s.origin[k] = h.origin[k];
     s.dims[k] = h.dims[k];
@@ -945,24 +955,10 @@ extern "C" int srt_model_create_scattered_file_root(const char *ptsfile, int yea
   return SRT_OK;
 }
 
-// ------------------------------------------------------------------------------------------ launches
-template <class K, class... Args>
-static void launch_wave_blocks(K kernel, long long n, hipStream_t st, Args... args) {
-  long long blocks = (n + WAVE - 1) / WAVE;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(WAVE), 0, st, args...);
-}
-
-struct DevBuf {
-  double *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t n) { return hipMalloc(&p, n * sizeof(double)) == hipSuccess ? 0 : -1; }
-};
-
+// ------------------------------------------------------------------------------------------ per-point entry points
 // a scratch allocation of the scattered model was refused: say so ONCE per model (the launch still runs -- without staging
 // every stencil takes the own-list path, without blocks every stencil scans its cells -- only slower), and do not try that
-// size again at every launch (LaunchSlot::*_failed; srt_model_trim forgets it)
+// size again at every launch (Scratch::failed; srt_model_trim forgets it)
 static void scratch_refused(srt_model *m, const char *what, size_t bytes) {
   if (m->warned_scratch) return;
   m->warned_scratch = true;
@@ -984,16 +980,14 @@ static bool blocks_enabled() {
 
 // scattered model: staging records for the one-wave blocks serving n items (srt_scattered.hpp shared_fit); beyond
 // 4096 blocks (2 GiB) the kernels run without (own-list path)
-static void stage_alloc(DevBuf &b, int64_t n) {
+static void stage_alloc(DevBuf<double> &b, int64_t n) {
   const int64_t blocks = (n + WAVE - 1) / WAVE;
-  if (!staging_enabled() || blocks > 4096 || b.alloc((size_t)blocks * ScatteredModel::REC_CAP * ScatteredModel::REC)) {
-    b.p = nullptr;
+  if (!staging_enabled() || blocks > 4096 || b.alloc((size_t)blocks * ScatteredModel::REC_CAP * ScatteredModel::REC) != hipSuccess)
     (void)hipGetLastError();
-  }
 }
 
-static int upload(DevBuf &b, const double *h, size_t n) {
-  if (b.alloc(n)) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+static int upload(DevBuf<double> &b, const double *h, size_t n) {
+  if (b.alloc(n) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
   HIP_OK(hipMemcpy(b.p, h, n * sizeof(double), hipMemcpyHostToDevice));
   return SRT_OK;
 }
@@ -1005,18 +999,16 @@ extern "C" int srt_plasma_params(srt_model *m, int64_t n, const double *x, doubl
   SRT_MODEL_SCOPE;
   int rc = ensure_model(m);
   if (rc) return rc;
-  DevBuf dx, dout;
+  DevBuf<double> dx, dout;
   if ((rc = upload(dx, x, 3 * n))) return rc;
-  if (dout.alloc(19 * n)) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-  if (m->kind == 1) launch_wave_blocks(params_kernel<NgoModel, false>, n, 0, (const NgoModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
-  else if (m->kind == 3) launch_wave_blocks(params_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
-  else if (m->kind == 4)
-    launch_wave_blocks(params_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
-  else if (m->kind == 5)
-    launch_wave_blocks(params_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
-  else if (m->kind == 6)
-    launch_wave_blocks(params_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, dout.p);
-  else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
+  if (dout.alloc(19 * n) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  rc = with_model(m, [&](auto tag) -> int {
+    using T = decltype(tag);
+    launch_wave_blocks(params_kernel<typename T::Model, T::lds>, n, 0, m->on_device<typename T::Model>(), m->d_common.p, (long long)n,
+                       dx.p, dout.p);
+    return SRT_OK;
+  });
+  if (rc) return rc;
   std::vector<double> h(19 * n);
   HIP_OK(hipMemcpy(h.data(), dout.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < n; ++i) {
@@ -1038,20 +1030,16 @@ extern "C" int srt_dispersion(srt_model *m, int64_t n, const double *x, const do
   SRT_MODEL_SCOPE;
   int rc = ensure_model(m);
   if (rc) return rc;
-  DevBuf dx, dk, dw, dout;
+  DevBuf<double> dx, dk, dw, dout;
   if ((rc = upload(dx, x, 3 * n)) || (rc = upload(dk, k, 3 * n)) || (rc = upload(dw, w, n))) return rc;
-  if (dout.alloc(10 * n)) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-  if (m->kind == 1)
-    launch_wave_blocks(dispersion_kernel<NgoModel, false>, n, 0, (const NgoModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
-  else if (m->kind == 3)
-    launch_wave_blocks(dispersion_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
-  else if (m->kind == 4)
-    launch_wave_blocks(dispersion_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
-  else if (m->kind == 5)
-    launch_wave_blocks(dispersion_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
-  else if (m->kind == 6)
-    launch_wave_blocks(dispersion_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, dout.p);
-  else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
+  if (dout.alloc(10 * n) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  rc = with_model(m, [&](auto tag) -> int {
+    using T = decltype(tag);
+    launch_wave_blocks(dispersion_kernel<typename T::Model, T::lds>, n, 0, m->on_device<typename T::Model>(), m->d_common.p,
+                       (long long)n, dx.p, dk.p, dw.p, dout.p);
+    return SRT_OK;
+  });
+  if (rc) return rc;
   HIP_OK(hipMemcpy(out, dout.p, 10 * n * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
 }
@@ -1062,13 +1050,12 @@ extern "C" int srt_is_right_handed(int64_t n, const double *in, int32_t *out) {
   DeviceScope srt_iscope_;
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
-  DevBuf din;
+  DevBuf<double> din;
+  DevBuf<int> dout;
   if ((rc = upload(din, in, 5 * n))) return rc;
-  int *d_out = nullptr;
-  HIP_OK(hipMalloc(&d_out, n * sizeof(int)));
-  hipLaunchKernelGGL(handedness_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (long long)n, (const double *)din.p, d_out);
-  hipError_t e = hipMemcpy(out, d_out, n * sizeof(int), hipMemcpyDeviceToHost);
-  (void)hipFree(d_out);
+  HIP_OK(dout.alloc(n));
+  hipLaunchKernelGGL(handedness_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (long long)n, (const double *)din.p, dout.p);
+  hipError_t e = hipMemcpy(out, dout.p, n * sizeof(int), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "handedness kernel: %s", hipGetErrorString(e));
   return SRT_OK;
 }
@@ -1079,24 +1066,20 @@ extern "C" int srt_gradients(srt_model *m, int64_t n, const double *x, const dou
   SRT_MODEL_SCOPE;
   int rc = ensure_model(m);
   if (rc) return rc;
-  DevBuf dx, dk, dw, dout;
+  DevBuf<double> dx, dk, dw, dout;
   if ((rc = upload(dx, x, 3 * n)) || (rc = upload(dk, k, 3 * n)) || (rc = upload(dw, w, n))) return rc;
-  if (dout.alloc(14 * n)) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-  if (m->kind == 1)
-    launch_wave_blocks(gradients_kernel<NgoModel, false>, n, 0, (const NgoModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, (double *)nullptr);
-  else if (m->kind == 3)
-    launch_wave_blocks(gradients_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, (double *)nullptr);
-  else if (m->kind == 4) {
-    DevBuf stage;
-    stage_alloc(stage, n);
-    launch_wave_blocks(gradients_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, stage.p);
-    HIP_OK(hipDeviceSynchronize()); // `stage` is freed at the end of this scope
-  }
-  else if (m->kind == 5)
-    launch_wave_blocks(gradients_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, (double *)nullptr);
-  else if (m->kind == 6)
-    launch_wave_blocks(gradients_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)dx.p, (const double *)dk.p, (const double *)dw.p, del, dout.p, (double *)nullptr);
-  else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
+  if (dout.alloc(14 * n) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  rc = with_model(m, [&](auto tag) -> int {
+    using T = decltype(tag);
+    using M = typename T::Model;
+    DevBuf<double> stage; // scattered model only; null for the others
+    if constexpr (std::is_same<M, ScatteredModel>::value) stage_alloc(stage, n);
+    launch_wave_blocks(gradients_kernel<M, T::lds>, n, 0, m->on_device<M>(), m->d_common.p, (long long)n, dx.p, dk.p, dw.p, del, dout.p,
+                       stage.p);
+    if constexpr (std::is_same<M, ScatteredModel>::value) HIP_OK(hipDeviceSynchronize()); // `stage` is freed at the end of this scope
+    return SRT_OK;
+  });
+  if (rc) return rc;
   HIP_OK(hipMemcpy(out, dout.p, 14 * n * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
 }
@@ -1107,69 +1090,38 @@ extern "C" int srt_rk_step(srt_model *m, int64_t n, const double *args, const do
   SRT_MODEL_SCOPE;
   int rc = ensure_model(m);
   if (rc) return rc;
-  DevBuf da, dd, dout;
+  DevBuf<double> da, dd, dout;
   if ((rc = upload(da, args, 7 * n)) || (rc = upload(dd, dt, n))) return rc;
-  if (dout.alloc(21 * n)) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-  if (m->kind == 1)
-    launch_wave_blocks(rkstep_kernel<NgoModel, false>, n, 0, (const NgoModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, (double *)nullptr);
-  else if (m->kind == 3)
-    launch_wave_blocks(rkstep_kernel<InterpModel, true>, n, 0, (const InterpModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, (double *)nullptr);
-  else if (m->kind == 4) {
-    DevBuf stage;
-    stage_alloc(stage, n);
-    launch_wave_blocks(rkstep_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, stage.p);
-    HIP_OK(hipDeviceSynchronize());
-  }
-  else if (m->kind == 5)
-    launch_wave_blocks(rkstep_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, (double *)nullptr);
-  else if (m->kind == 6)
-    launch_wave_blocks(rkstep_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)m->d_model, (const Common *)m->d_common, (long long)n, (const double *)da.p, (const double *)dd.p, del, dout.p, (double *)nullptr);
-  else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
+  if (dout.alloc(21 * n) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  rc = with_model(m, [&](auto tag) -> int {
+    using T = decltype(tag);
+    using M = typename T::Model;
+    DevBuf<double> stage; // scattered model only; null for the others
+    if constexpr (std::is_same<M, ScatteredModel>::value) stage_alloc(stage, n);
+    launch_wave_blocks(rkstep_kernel<M, T::lds>, n, 0, m->on_device<M>(), m->d_common.p, (long long)n, da.p, dd.p, del, dout.p, stage.p);
+    if constexpr (std::is_same<M, ScatteredModel>::value) HIP_OK(hipDeviceSynchronize()); // `stage` is freed at the end of this scope
+    return SRT_OK;
+  });
+  if (rc) return rc;
   HIP_OK(hipMemcpy(out, dout.p, 21 * n * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
 }
 
 
 // ---- the random / adaptive sample-set builder (kernels and the level-by-level scheme: srt_sampler.hpp) ----
-namespace {
-struct DevMem { // grow-only device buffer
-  void *p = nullptr;
-  size_t cap = 0;
-  ~DevMem() {
-    if (p) (void)hipFree(p);
-  }
-  // at least `bytes`; the first `keep` bytes survive a reallocation
-  int reserve(size_t bytes, size_t keep = 0) {
-    if (bytes <= cap) return 0;
-    size_t want = bytes + bytes / 2 + 4096;
-    void *q = nullptr;
-    if (hipMalloc(&q, want) != hipSuccess) return -1;
-    if (p && keep && hipMemcpy(q, p, keep, hipMemcpyDeviceToDevice) != hipSuccess) {
-      (void)hipFree(q);
-      return -1;
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = want;
-    return 0;
-  }
-  template <class T> T *as() { return (T *)p; }
-};
-} // namespace
-
-static void smp_eval(srt_model *src, long long n, double *rec) {
-  if (n <= 0) return;
-  if (src->kind == 1) launch_wave_blocks(smp_eval_kernel<NgoModel, false>, n, 0, (const NgoModel *)src->d_model, n, rec);
-  else if (src->kind == 3) launch_wave_blocks(smp_eval_kernel<InterpModel, true>, n, 0, (const InterpModel *)src->d_model, n, rec);
-  else if (src->kind == 5) launch_wave_blocks(smp_eval_kernel<Ngo3dModel, false>, n, 0, (const Ngo3dModel *)src->d_model, n, rec);
-  else if (src->kind == 6) launch_wave_blocks(smp_eval_kernel<Simple3dModel, false>, n, 0, (const Simple3dModel *)src->d_model, n, rec);
-  else launch_wave_blocks(smp_eval_kernel<ScatteredModel, true>, n, 0, (const ScatteredModel *)src->d_model, n, rec);
+static int smp_eval(srt_model *src, long long n, double *rec) {
+  if (n <= 0) return SRT_OK;
+  return with_model(src, [&](auto tag) -> int {
+    using T = decltype(tag);
+    launch_wave_blocks(smp_eval_kernel<typename T::Model, T::lds>, n, 0, src->on_device<typename T::Model>(), n, rec);
+    return SRT_OK;
+  });
 }
 
 extern "C" int srt_build_samples(srt_model *src, const srt_sampler_params *sp, int64_t n_in, const double *in_pts,
                                  int64_t *n_out, double **out, int64_t stage_counts[6]) {
   if (!src || !sp || !n_out || !out || n_in < 0 || (n_in > 0 && !in_pts)) return srt_set_error(SRT_EINVAL, "bad argument");
-  if (src->kind != 1 && src->kind != 3 && src->kind != 4 && src->kind != 5 && src->kind != 6) return srt_set_error(SRT_EINVAL, "model kind %d unsupported", src->kind);
+  if (const int bad = with_model(src, [](auto) -> int { return SRT_OK; })) return bad; // an unknown kind fails before anything is allocated
   const double *bd = sp->bounds;
   if (!(bd[1] > bd[0]) || !(bd[3] > bd[2]) || !(bd[5] > bd[4])) return srt_set_error(SRT_EINVAL, "empty bounds");
   if (sp->n_zero_altitude < 0 || sp->n_iri_pad < 0 || sp->n_initial_radial < 0 || sp->n_initial_uniform < 0 || sp->max_recursion < 0 ||
@@ -1189,7 +1141,7 @@ extern "C" int srt_build_samples(srt_model *src, const srt_sampler_params *sp, i
   root.id = 1;
   int64_t counts[6] = {n_in, 0, 0, 0, 0, 0};
   const size_t RB = SMP_REC * sizeof(double);
-  DevMem pool, slot, stage, valid;
+  DevBytes pool, slot, stage, valid;
   long long npool = 0;
 #define SMP_OK(expr)                                                                        \
   do {                                                                                      \
@@ -1218,7 +1170,7 @@ extern "C" int srt_build_samples(srt_model *src, const srt_sampler_params *sp, i
     SMP_MEM(valid.reserve((size_t)n * sizeof(int)));
     hipLaunchKernelGGL(smp_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stg, n, (unsigned long long)sp->seed, root, rmin,
                        rmax, stage.as<double>(), valid.as<int>());
-    smp_eval(src, n, stage.as<double>());
+    if (const int bad = smp_eval(src, n, stage.as<double>())) return bad;
     SMP_OK(hipDeviceSynchronize());
     if (to_pool) {
       std::vector<int> hv((size_t)n);
@@ -1258,8 +1210,8 @@ extern "C" int srt_build_samples(srt_model *src, const srt_sampler_params *sp, i
 
   // (3) adaptive (:298-347): tol halves until adaptive_nmax adaptive samples exist
   if (sp->adaptive_nmax > 0) {
-    DevMem keys0, keys1, idx0, idx1, sorttmp, callsA, callsB, halves, cand, nadd, refine, addA, addoff, childoff, scantmp;
-    DevMem *calls = &callsA, *children = &callsB;
+    DevBytes keys0, keys1, idx0, idx1, sorttmp, callsA, callsB, halves, cand, nadd, refine, addA, addoff, childoff, scantmp;
+    DevBytes *calls = &callsA, *children = &callsB;
     int64_t nsamples = 0;
     double tol = sp->initial_tol;
     for (int pass = 0; nsamples < sp->adaptive_nmax && pass < max_passes; ++pass, tol = tol / 2.0) {
@@ -1293,7 +1245,7 @@ extern "C" int srt_build_samples(srt_model *src, const srt_sampler_params *sp, i
         }
         hipLaunchKernelGGL(smp_cand_kernel, dim3((unsigned)((ncand + 255) / 256)), dim3(256), 0, 0, (int)nhalf, calls->as<SmpBox>(), dim,
                            (unsigned long long)sp->seed, (unsigned long long)pass, ninc, halves.as<SmpBox>(), cand.as<double>());
-        smp_eval(src, ncand, cand.as<double>());
+        if ((rc = smp_eval(src, ncand, cand.as<double>()))) return rc;
         hipLaunchKernelGGL(smp_stats_kernel, dim3((unsigned)nhalf), dim3(WAVE), 0, 0, (int)nhalf, npool, keys1.as<unsigned>(), idx1.as<int>(),
                            pool.as<double>(), cand.as<double>(), halves.as<SmpBox>(), dim, nspec, ninc, tol, nadd.as<int>(), refine.as<int>(),
                            addA.as<int>());
@@ -1399,6 +1351,24 @@ __global__ void ray_keys_kernel(const InterpModel *mp, const double *pos0 /* SoA
   ids[i] = (int)i;
 }
 
+// scattered model: one of a slot's two scratch blocks, `per_block` doubles for each one-wave block of the grid, regrown when the
+// grid outgrows it; *out = null when it was refused
+static int slot_scratch(srt_model *m, srt_model::LaunchSlot &sl, srt_model::Scratch &s, long long grid, size_t per_block,
+                        const char *what, double **out) {
+  if (grid > s.blocks && !(s.failed > 0 && grid >= s.failed)) {
+    if (sl.used) HIP_OK(hipEventSynchronize(sl.done)); // about to free what that launch may still read
+    s.blocks = 0;
+    if (s.buf.alloc((size_t)grid * per_block) == hipSuccess) s.blocks = grid;
+    else {
+      (void)hipGetLastError();
+      s.failed = grid;
+      scratch_refused(m, what, (size_t)grid * per_block * sizeof(double));
+    }
+  }
+  *out = grid <= s.blocks ? s.buf.p : nullptr;
+  return SRT_OK;
+}
+
 extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t nrays, const double *d_pos0,
                                       const double *d_dir0, const double *d_w0, double *d_rows, int32_t *d_nrows,
                                       int32_t *d_stopcond, int64_t *d_counters, void *stream) {
@@ -1428,12 +1398,12 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   a.order = nullptr;
   HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
   // persistent grid: enough one-wave blocks to fill the chip, never more than the rays need
-  // interp: 34 KiB of LDS per wave, 512 registers per lane: one wave per SIMD; scattered: 18.5 KiB, <= 256 registers: two
-  // ngo3d: the Ngo kernels with a plasmapause head per point; the default WaveBudget, as Ngo
-  // simple3d: as Ngo -- the default WaveBudget (one wave per SIMD).  Its density body needs 148 registers, but the integrator
-  // around it is what fills the budget: 376 .. 394 registers with the dipole field, 512 with T04_s, the same as the Ngo kernels;
-  // two waves per SIMD (256 registers) would spill the integrator's state on every trip.
-  int per_cu = m->kind == 3 ? 4 : (m->kind == 4 ? 4 * ScatteredModel::WAVES_PER_EU : 8);
+  int per_cu = 0;
+  rc = with_model(m, [&](auto tag) -> int {
+    per_cu = decltype(tag)::waves_per_cu;
+    return SRT_OK;
+  });
+  if (rc) return rc;
   if (const char *e = getenv("SRT_WAVES_PER_CU")) {
     const int v = atoi(e);
     if (v >= 1 && v <= per_cu) per_cu = v;
@@ -1472,99 +1442,66 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   if (sl.used) HIP_OK(hipStreamWaitEvent(st, sl.done, 0)); // the slot's previous launch (maybe on another stream) is over
   srt_model::LaunchTimes &lt = m->hist[m->next_hist];
   HIP_OK(hipEventRecord(lt.ev0, st));
-  if (p->ray_order >= 1 && m->kind == 3 && nrays > WAVE && nrays < (1ll << 31) && m->interp.ax.n < 1023 &&
-      m->interp.ay.n < 1023 && m->interp.az.n < 1023) {
+  const InterpModel &im = m->as<InterpModel>();
+  if (p->ray_order >= 1 && m->kind == KIND_INTERP && nrays > WAVE && nrays < (1ll << 31) && im.ax.n < 1023 && im.ay.n < 1023 &&
+      im.az.n < 1023) {
     // work through the launch set in the order of the rays' launch cells (inside the timed region)
-    if ((size_t)nrays > sl.sort_cap) {
+    if ((size_t)nrays > sl.ids[1].cap) {
       if (sl.used) HIP_OK(hipEventSynchronize(sl.done)); // about to free what that launch may still read
+      // all four are dropped before the first is allocated, and ids[1] comes last: after a refused allocation it is empty, so
+      // the next launch on this slot allocates all four again
       for (int k = 0; k < 2; ++k) {
-        if (sl.d_keys[k]) (void)hipFree(sl.d_keys[k]);
-        if (sl.d_ids[k]) (void)hipFree(sl.d_ids[k]);
-        sl.d_keys[k] = nullptr;
-        sl.d_ids[k] = nullptr;
+        sl.keys[k].release();
+        sl.ids[k].release();
       }
-      sl.sort_cap = 0;
       for (int k = 0; k < 2; ++k) {
-        HIP_OK(hipMalloc(&sl.d_keys[k], (size_t)nrays * sizeof(unsigned)));
-        HIP_OK(hipMalloc(&sl.d_ids[k], (size_t)nrays * sizeof(int)));
+        HIP_OK(sl.keys[k].alloc((size_t)nrays));
+        HIP_OK(sl.ids[k].alloc((size_t)nrays));
       }
-      sl.sort_cap = (size_t)nrays;
     }
     size_t need = 0;
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, sl.d_keys[0], sl.d_keys[1], sl.d_ids[0], sl.d_ids[1], (int)nrays, 0, 31, st));
-    if (need > sl.sorttmp_bytes) {
+    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, sl.keys[0].p, sl.keys[1].p, sl.ids[0].p, sl.ids[1].p, (int)nrays, 0, 31, st));
+    if (need > sl.sorttmp.cap) {
       if (sl.used) HIP_OK(hipEventSynchronize(sl.done));
-      if (sl.d_sorttmp) (void)hipFree(sl.d_sorttmp);
-      sl.d_sorttmp = nullptr;
-      sl.sorttmp_bytes = 0;
-      HIP_OK(hipMalloc(&sl.d_sorttmp, need));
-      sl.sorttmp_bytes = need;
+      HIP_OK(sl.sorttmp.alloc(need));
     }
-    hipLaunchKernelGGL(ray_keys_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, st, (const InterpModel *)m->d_model,
-                       d_pos0, d_dir0, d_w0, p->ray_order == 2 ? 1 : 0, (long long)nrays, sl.d_keys[0], sl.d_ids[0]);
-    size_t tb = sl.sorttmp_bytes;
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(sl.d_sorttmp, tb, sl.d_keys[0], sl.d_keys[1], sl.d_ids[0], sl.d_ids[1], (int)nrays, 0, 31, st));
-    a.order = sl.d_ids[1];
+    hipLaunchKernelGGL(ray_keys_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, st, m->on_device<InterpModel>(), d_pos0,
+                       d_dir0, d_w0, p->ray_order == 2 ? 1 : 0, (long long)nrays, sl.keys[0].p, sl.ids[0].p);
+    size_t tb = sl.sorttmp.cap;
+    HIP_OK(hipcub::DeviceRadixSort::SortPairs(sl.sorttmp.p, tb, sl.keys[0].p, sl.keys[1].p, sl.ids[0].p, sl.ids[1].p, (int)nrays, 0, 31, st));
+    a.order = sl.ids[1].p;
   }
-  a.scratch = nullptr;
-  if (m->kind == 4 && staging_enabled()) { // without the buffer the kernel still runs (own-list path everywhere), only slower
-    if (grid > sl.stage_blocks && !(sl.stage_failed > 0 && grid >= sl.stage_failed)) {
-      if (sl.used) HIP_OK(hipEventSynchronize(sl.done));
-      if (sl.d_stage) (void)hipFree(sl.d_stage);
-      sl.d_stage = nullptr;
-      sl.stage_blocks = 0;
-      const size_t bytes = (size_t)grid * ScatteredModel::REC_CAP * ScatteredModel::REC * sizeof(double);
-      if (hipMalloc(&sl.d_stage, bytes) == hipSuccess) sl.stage_blocks = grid;
-      else {
-        (void)hipGetLastError();
-        sl.stage_failed = grid;
-        scratch_refused(m, "staging records", bytes);
-      }
-    }
-    a.scratch = grid <= sl.stage_blocks ? sl.d_stage : nullptr;
-  }
-  a.scratch2 = nullptr;
-  if (m->kind == 4 && a.scratch != nullptr && blocks_enabled()) { // without them the kernel scans the cells for every stencil
-    if (grid > sl.cand_blocks && !(sl.cand_failed > 0 && grid >= sl.cand_failed)) {
-      if (sl.used) HIP_OK(hipEventSynchronize(sl.done));
-      if (sl.d_blocks) (void)hipFree(sl.d_blocks);
-      sl.d_blocks = nullptr;
-      sl.cand_blocks = 0;
-      const size_t bytes = (size_t)grid * ScatteredModel::BLOCK_DOUBLES * sizeof(double);
-      if (hipMalloc(&sl.d_blocks, bytes) == hipSuccess) sl.cand_blocks = grid;
-      else {
-        (void)hipGetLastError();
-        sl.cand_failed = grid;
-        scratch_refused(m, "candidate blocks", bytes);
-      }
-    }
-    a.scratch2 = grid <= sl.cand_blocks ? sl.d_blocks : nullptr;
-  }
+  // scattered model: without the staging records the kernel still runs (own-list path everywhere), without the candidate blocks
+  // it scans the cells for every stencil -- only slower
+  a.scratch = a.scratch2 = nullptr;
+  if (m->kind == KIND_SCATTERED && staging_enabled() &&
+      (rc = slot_scratch(m, sl, sl.stage, grid, (size_t)ScatteredModel::REC_CAP * ScatteredModel::REC, "staging records", &a.scratch)))
+    return rc;
+  if (m->kind == KIND_SCATTERED && a.scratch != nullptr && blocks_enabled() &&
+      (rc = slot_scratch(m, sl, sl.cand, grid, ScatteredModel::BLOCK_DOUBLES, "candidate blocks", &a.scratch2)))
+    return rc;
   const bool fixed = p->fixedstep != 0;
   const int fopt = m->cm.fld.use_tsy != 0 ? 2 : (m->cm.fld.use_igrf != 0 ? 1 : 0);
   // one instantiation per (model, integrator, field option): the dipole kernels carry none of the IGRF code, the
   // IGRF-alone kernels none of the T04 call sites
-#define SRT_LAUNCH_TRACE1(MODEL, LDS, FIX)                                                                                       \
-  do {                                                                                                                           \
-    if (fopt == 2) hipLaunchKernelGGL((trace_kernel<MODEL, FIX, LDS, 2>), dim3((unsigned)grid), dim3(WAVE), 0, st, dm, dc, a);   \
-    else if (fopt == 1) hipLaunchKernelGGL((trace_kernel<MODEL, FIX, LDS, 1>), dim3((unsigned)grid), dim3(WAVE), 0, st, dm, dc, a); \
-    else hipLaunchKernelGGL((trace_kernel<MODEL, FIX, LDS, 0>), dim3((unsigned)grid), dim3(WAVE), 0, st, dm, dc, a);             \
-  } while (0)
-#define SRT_LAUNCH_TRACE(MODEL, LDS)                                                                                             \
-  do {                                                                                                                           \
-    const MODEL *dm = (const MODEL *)m->d_model;                                                                                 \
-    const Common *dc = (const Common *)m->d_common;                                                                              \
-    if (fixed) SRT_LAUNCH_TRACE1(MODEL, LDS, true);                                                                              \
-    else SRT_LAUNCH_TRACE1(MODEL, LDS, false);                                                                                   \
-  } while (0)
-  if (m->kind == 1) SRT_LAUNCH_TRACE(NgoModel, false);
-  else if (m->kind == 3) SRT_LAUNCH_TRACE(InterpModel, true);
-  else if (m->kind == 4) SRT_LAUNCH_TRACE(ScatteredModel, true);
-  else if (m->kind == 5) SRT_LAUNCH_TRACE(Ngo3dModel, false);
-  else if (m->kind == 6) SRT_LAUNCH_TRACE(Simple3dModel, false);
-  else return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
-#undef SRT_LAUNCH_TRACE
-#undef SRT_LAUNCH_TRACE1
+  rc = with_model(m, [&](auto tag) -> int {
+    using T = decltype(tag);
+    using M = typename T::Model;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVE), 0, st, m->on_device<M>(), m->d_common.p, a);
+    };
+    if (fixed) {
+      if (fopt == 2) launch(trace_kernel<M, true, T::lds, 2>);
+      else if (fopt == 1) launch(trace_kernel<M, true, T::lds, 1>);
+      else launch(trace_kernel<M, true, T::lds, 0>);
+    } else {
+      if (fopt == 2) launch(trace_kernel<M, false, T::lds, 2>);
+      else if (fopt == 1) launch(trace_kernel<M, false, T::lds, 1>);
+      else launch(trace_kernel<M, false, T::lds, 0>);
+    }
+    return SRT_OK;
+  });
+  if (rc) return rc;
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(lt.ev1, st));
   HIP_OK(hipEventRecord(sl.done, st));
@@ -1581,7 +1518,7 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   }
 #endif
 #ifdef SRT_PHASE_TIMING
-  if (m->kind == 4 && getenv("SRT_PHASE_TIMING")) {
+  if (m->kind == KIND_SCATTERED && getenv("SRT_PHASE_TIMING")) {
     unsigned long long h[16];
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpyFromSymbol(h, HIP_SYMBOL(srt_phase_cycles), sizeof h));
@@ -1699,22 +1636,20 @@ extern "C" int srt_damping(const srt_damping_params *dp, int nspec, const double
   if (rc) return rc;
   if (nrays == 0) return SRT_OK;
   const size_t nr = (size_t)nrays * slots;
-  DevBuf d_rows, d_w0, d_rate, d_mag;
-  int *d_nrows = nullptr, *d_flag = nullptr;
+  DevBuf<double> d_rows, d_w0, d_rate, d_mag;
+  DevBuf<int> d_nrows, d_flag;
   if ((rc = upload(d_rows, rows, nr * SRT_ROW)) || (rc = upload(d_w0, w0, nrays))) return rc;
-  if (d_rate.alloc(nr) || d_mag.alloc(nr)) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-  hipError_t e = hipMalloc(&d_nrows, nrays * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&d_flag, nr * sizeof(int));
-  if (e == hipSuccess) e = hipMemcpy(d_nrows, nrows, nrays * sizeof(int), hipMemcpyHostToDevice);
+  if (d_rate.alloc(nr) != hipSuccess || d_mag.alloc(nr) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  hipError_t e = d_nrows.alloc(nrays);
+  if (e == hipSuccess) e = d_flag.alloc(nr);
+  if (e == hipSuccess) e = hipMemcpy(d_nrows.p, nrows, nrays * sizeof(int), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    rc = srt_damping_device(dp, nspec, qs, ms, slots, outputper, nrays, d_rows.p, d_nrows, d_w0.p, d_rate.p, d_mag.p, d_flag, nullptr);
+    rc = srt_damping_device(dp, nspec, qs, ms, slots, outputper, nrays, d_rows.p, d_nrows.p, d_w0.p, d_rate.p, d_mag.p, d_flag.p, nullptr);
     if (!rc) e = hipDeviceSynchronize();
     if (!rc && e == hipSuccess) e = hipMemcpy(rate, d_rate.p, nr * sizeof(double), hipMemcpyDeviceToHost);
     if (!rc && e == hipSuccess && magnitude) e = hipMemcpy(magnitude, d_mag.p, nr * sizeof(double), hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && flag) e = hipMemcpy(flag, d_flag, nr * sizeof(int), hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && flag) e = hipMemcpy(flag, d_flag.p, nr * sizeof(int), hipMemcpyDeviceToHost);
   }
-  if (d_nrows) (void)hipFree(d_nrows);
-  if (d_flag) (void)hipFree(d_flag);
   if (rc) return rc;
   if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "damping: %s", hipGetErrorString(e));
   return SRT_OK;

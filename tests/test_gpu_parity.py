@@ -17,13 +17,10 @@ import numpy as np
 import pytest
 
 from conftest import DELS, G3_INTERP_BARS, vrel
+from dispersion_checks import f_scale, rel
 
 pytestmark = pytest.mark.gpu
 MODELS = ["ngo", "ngoducts", "interp"]
-
-
-def rel(a, b):
-    return np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
 
 
 @pytest.mark.parametrize("name", MODELS)
@@ -52,12 +49,6 @@ def test_g0_interp_out_of_range_and_nodes(gpu_models, oracle_models, grid16):
     g = gpu_models["interp"].plasma_params(pts)
     o = np.array([np.concatenate(oracle_models["interp"].plasma_params(p)) for p in pts])
     assert rel(g[:, 4:8], o[:, 4:8]).max() <= 1e-11
-
-
-def f_scale(rows, out, c):
-    n2 = (np.linalg.norm(rows[:, 3:6], axis=1) * c / rows[:, 6]) ** 2
-    S, D, P, R, L = (out[:, i] for i in range(1, 6))
-    return (np.abs(S) + np.abs(P)) * n2 ** 2 + (np.abs(R * L) + np.abs(P * S)) * 2 * n2 + np.abs(R * L * P)
 
 
 @pytest.mark.parametrize("name", MODELS)

@@ -68,6 +68,12 @@ def sens_rel(s, ref):
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
+def test_g1_dispersion_from_own_plasma_params(gold, models, tag):
+    from dispersion_checks import check_dispersion_against_own_params
+    check_dispersion_against_own_params(models[tag], gold["g23_state_" + tag])
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
 def test_g2_gradients_and_right_hand_side(gold, models, tag):
     st, ref, sn = gold["g23_state_" + tag], gold["g2_" + tag], gold["g2_sens_" + tag]
     g = models[tag].gradients(st[:, 0:3], st[:, 3:6], st[:, 6], DEL)
