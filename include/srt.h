@@ -7,15 +7,16 @@
  *                        raytracer_stopconditions)            (signature fortran/raytracer.f95:609-642)
  * becomes one batched call, srt_trace_batch().  The reference's plugin callback
  *     subroutine funcPlasmaParams(x, qs, Ns, ms, nus, B0, funcPlasmaParamsData)   (raytracer.f95:121-129)
- * cannot be a host callback on a GPU path; its five in-scope implementations are selected by the
- * model handle instead (modelnum 1 / 3 / 4 / 5 / 6 of raytracer_driver.f95:256-992) and are exposed for
+ * cannot be a host callback on a GPU path; its six in-scope implementations are selected by the
+ * model handle instead (modelnum 1 / 3 / 4 / 5 / 6 / 7 of raytracer_driver.f95:256-1136) and are exposed for
  * point queries through srt_plasma_params().
  *
  * Conventions: plain pointers and sizes, no C++ or torch types.  All arrays are HOST memory unless a
  * function name ends in _device.  Vectors are AoS: pos0[i*3+c].  Every function returns 0 on success
  * or a negative SRT_E* code; srt_last_error() gives the text.  Per-ray failures never abort a batch:
  * they are reported through stopcond (same codes as raytracer.f95:324-353, plus SRT_STOP_NUMERIC for
- * the reference's process-killing `stop` on an SVD failure, blas.f95:208-211, or in modelnum 6's check_crossing).
+ * the reference's process-killing `stop` on an SVD failure, blas.f95:208-211, or in modelnum 6's check_crossing, and for
+ * a field line of modelnum 7 that has not ended after 500 points).
  * The library needs a gfx950 GPU; there is no CPU fallback.
  */
 #ifndef SRT_H
@@ -139,6 +140,26 @@ int srt_model_create_scattered_file_root(const char *ptsfile, int yearday, int m
  * del = 1e-6.  Kind 5, four species (electrons, H+, He+, O+). */
 int srt_model_create_ngo3d(const char *configfile, double kp, int fixed_MLT, double MLT, int yearday, int msec, srt_model **out);
 int srt_model_create_simple3d(double kp, int fixed_MLT, double MLT, int yearday, int msec, srt_model **out);
+/* modelnum=7: AT64ThCh_adapter.f95, a diffusive-equilibrium plasmasphere (electrons, O+, H+: kind 7, three species) whose
+ * electron density above 400 km is scaled by |B(point)| / |B(foot)|: for EVERY evaluated point geopack's TRACE_08 follows the
+ * field line of T04_s + IGRF from the point to the sphere r = R_E + 400 km (srt_field_line_foot below is that trace alone).
+ * gcpm_kp = the driver's --gcpm_kp, an integer; parmod = the ten --tsyganenko_* values; igrf_coeff_file as for
+ * srt_model_set_field (NULL = the table shipped with the library).  The trace always uses T04_s and IGRF, whatever
+ * srt_model_set_field says later: use_igrf / use_tsyganenko choose only the base field of |B(point)| and the returned B0, so the
+ * model always owns a coefficient table and parmod (srt_model_set_tsyganenko_params replaces the latter).  A point at or below
+ * 400 km takes the ratio 1 without a trace; a line that leaves through the outer boundary (r > 60, y^2 + z^2 > 1600, x > 20 R_E or
+ * more than four reversals) has no foot on the sphere, and |B(foot)| is IGRF wherever the trace stopped, as in the Fortran.
+ * The driver's step for this model is del = 1e-4.
+ * Three things the adapter leaves undefined, and what this library does:
+ *  1. it hands its DOUBLE parmod to TRACE_08, whose PARMOD is REAL, so the reference's trace runs T04_s on reinterpreted bytes
+ *     (Pdyn = 0 for the usual --tsyganenko_Pdyn=4; a segmentation fault for 1.7).  Here the trace sees real(parmod), as the
+ *     adapter's own final T04_s call does.
+ *  2. its local `psi`, read by that final T04_s call (use_tsyganenko = 1), is never set; the reference's toolchain zeroes
+ *     locals, so it is 0 here.  The trace itself uses geopack's own dipole tilt PSI for the date (RECALC_08).
+ *  3. TRACE_08's bounds check is commented out and the adapter's arrays hold 500 points.  Here a line that has not ended after
+ *     500 points (or whose step was halved 64 times in a row) gives NaN densities, and a traced ray ends with SRT_STOP_NUMERIC. */
+int srt_model_create_at64thch(int gcpm_kp, const double parmod[10], const char *igrf_coeff_file, int yearday, int msec,
+                              srt_model **out);
 /* The step before the path: sample a model's funcPlasmaParams on a regular nx x ny x nz grid in
  * log space ON THE DEVICE -- gcpm_dens_model_buildgrid.f95:160-300 with any model handle in place of GCPM.
  * compder = 1 adds the seven explicit finite-difference blocks (d = 1e-3*|pos|, :197-296); compder = 0 leaves the
@@ -185,7 +206,7 @@ int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenko, const ch
 /* parmod[10] = Pdyn (nPa), Dst (nT), ByIMF, BzIMF (nT), W1 .. W6: the driver's --tsyganenko_* flags */
 int srt_model_set_tsyganenko_params(srt_model *m, const double parmod[10]);
 void srt_model_destroy(srt_model *m);
-int srt_model_kind(const srt_model *m);  /* 1, 3, 4, 5 or 6 */
+int srt_model_kind(const srt_model *m);  /* 1, 3, 4, 5, 6 or 7 */
 int srt_model_nspec(const srt_model *m);
 int srt_model_species(const srt_model *m, double qs[SRT_MAXSPEC], double ms[SRT_MAXSPEC]);
 int64_t srt_model_device_bytes(const srt_model *m);
@@ -208,6 +229,14 @@ int srt_gradients(srt_model *m, int64_t n, const double *x, const double *k, con
  * (raytracer.f95:504-596) */
 int srt_rk_step(srt_model *m, int64_t n, const double *args, const double *dt, double del,
                 double *out);
+/* geopack's TRACE_08 (geopack2008.for:1649-1840), batched: the field line of T04_s + IGRF from x[n][3] (SM, metres) with the
+ * AT64ThCh adapter's constants (DIR 1, DSMAX 1, ERR 1e-4, RLIM 60, R0 = (R_E + 400 km) / R_E), in default REAL like the Fortran.
+ * out[n][6] = XF, YF, ZF (GSM, Earth radii), |IGRF| there (nT), how the line ended, TRACE_08's L (number of points).
+ * Endings: 0 the foot on the sphere r = R0 (interpolated between the last two points), 1 the outer boundary (r > RLIM,
+ * y^2 + z^2 > 1600 or x > 20), 2 more than four reversals of the radial direction, 3 no end within 500 points (NaN).
+ * Works on a handle of any kind whose coefficient table is loaded (srt_model_set_field with use_igrf or use_tsyganenko, or a
+ * modelnum-7 handle) and whose parmod is set (srt_model_set_tsyganenko_params, or a modelnum-7 handle): SRT_EINVAL otherwise. */
+int srt_field_line_foot(srt_model *m, int64_t n, const double *x, double *out);
 
 /* ---- the hot path: replaces the driver's whole ray loop ---- */
 /* slots per ray = ceil(maxsteps/outputper) */

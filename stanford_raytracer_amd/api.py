@@ -83,6 +83,8 @@ def lib():
                                                        C.c_double, C.c_int64, C.POINTER(vp)]
     L.srt_model_create_simple3d.argtypes = [C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
     L.srt_model_create_ngo3d.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]
+    L.srt_model_create_at64thch.argtypes = [C.c_int, dp, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
+    L.srt_field_line_foot.argtypes = [vp, C.c_int64, dp, dp]
     L.srt_model_set_field.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
     L.srt_model_set_tsyganenko_params.argtypes = [vp, dp]
     L.srt_model_destroy.argtypes = [vp]
@@ -233,6 +235,29 @@ class Model:
         _check(lib().srt_model_create_ngo3d(os.fsencode(configfile), float(kp), fixed,
                                             0.0 if fixed_mlt is None else float(fixed_mlt), yearday, msec, C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def at64thch(cls, gcpm_kp, parmod, yearday=2010001, msec=0, igrf_coeff_file=None):
+        """modelnum 7, the AT64ThCh diffusive-equilibrium plasmasphere (AT64ThCh_adapter.f95): above 400 km the electron density
+        is scaled by |B(point)| / |B(foot)|, the foot found by a field-line trace through T04_s + IGRF for every evaluated
+        point.  gcpm_kp: the driver's --gcpm_kp, an integer; parmod = Pdyn, Dst, ByIMF, BzIMF, W1..W6 (--tsyganenko_*), always
+        needed: the trace uses T04_s and IGRF whatever set_field() says (include/srt.h has the three decisions on what the
+        adapter leaves undefined)."""
+        if int(gcpm_kp) != gcpm_kp:
+            raise ValueError("gcpm_kp is an integer")
+        h = C.c_void_p()
+        _check(lib().srt_model_create_at64thch(int(gcpm_kp), _dp(_f64(parmod, (10,))),
+                                               os.fsencode(igrf_coeff_file) if igrf_coeff_file else None, yearday, msec, C.byref(h)))
+        return cls(h)
+
+    def field_line_foot(self, x):
+        """geopack's TRACE_08 from x[n,3] (SM, metres) through T04_s + IGRF with the AT64ThCh adapter's constants ->
+        [n,6] = XF, YF, ZF (GSM, R_E), |IGRF| there (nT), ending (0 sphere, 1 outer boundary, 2 reversals, 3 no end within 500
+        points: NaN), number of points.  The handle needs a coefficient table and parmod (set_field(..., parmod=...))."""
+        x = _f64(x, (-1, 3))
+        out = np.zeros((x.shape[0], 6))
+        _check(lib().srt_field_line_foot(self.h, x.shape[0], _dp(x), _dp(out)))
+        return out
 
     def build_grid(self, nx, ny, nz, bounds, compder=False):
         """Sample this model on a regular grid in log space on the device (the reference's grid builder with this

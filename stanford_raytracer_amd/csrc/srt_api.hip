@@ -24,6 +24,7 @@
 #include "srt_ngo_setup.hpp"
 #include "srt_scattered.hpp"
 #include "srt_simple3d.hpp"
+#include "srt_at64thch.hpp"
 #include "srt_sampler.hpp"
 #include "srt_damping.hpp"
 #include <hipcub/hipcub.hpp>
@@ -180,13 +181,17 @@ extern "C" int srt_device_info(char *name, int name_len, int *cu_count, int64_t 
 }
 
 // ------------------------------------------------------------------------------------------ model
-enum ModelKind { KIND_NGO = 1, KIND_INTERP = 3, KIND_SCATTERED = 4, KIND_NGO3D = 5, KIND_SIMPLE3D = 6 }; // the driver's modelnum
+enum ModelKind { KIND_NGO = 1, KIND_INTERP = 3, KIND_SCATTERED = 4, KIND_NGO3D = 5, KIND_SIMPLE3D = 6, KIND_AT64THCH = 7 }; // the driver's modelnum
 
 struct srt_model {
   int kind = 0, nspec = 0;
   int device = current_device(); // the HIP device the tables live on (the creating thread's)
   Common cm{};
-  std::tuple<NgoModel, InterpModel, ScatteredModel, Ngo3dModel, Simple3dModel> host{}; // the host copy of `kind`'s struct
+  // what srt_field_line_foot (and modelnum 7's trace) needs beyond Common: has the coefficient table been loaded, has parmod been
+  // set, and geopack's own PSI for the table's date (srt_host::igrf_setup)
+  bool have_table = false, have_parmod = false;
+  float geopack_psi = 0.f;
+  std::tuple<NgoModel, InterpModel, ScatteredModel, Ngo3dModel, Simple3dModel, At64ThChModel> host{}; // the host copy of `kind`'s struct
   template <class M> M &as() { return std::get<M>(host); }
   DevBuf<double> d_pts;
   DevBuf<double> d_xyz; // scattered model: the sample positions once more, SoA [3][npts] (the candidate scans read only these)
@@ -194,6 +199,9 @@ struct srt_model {
   DevBuf<double> d_coef;
   DevBytes d_model; // device copy of the host struct (kernels read it through scalar loads)
   template <class M> const M *on_device() const { return (const M *)d_model.p; }
+  // Allocated ONCE, in model_finish, and never reallocated: modelnum 7's struct holds a device pointer into it
+  // (At64ThChModel::fld = &d_common.p->fld, set by upload_constants).  Whoever reallocates it, or copies a handle, has to call
+  // upload_constants again.
   DevBuf<Common> d_common;
   int64_t device_bytes = 0;
   int cu_count = 256;
@@ -268,7 +276,7 @@ static void launch_wave_blocks(K kernel, long long n, hipStream_t st, Args... ar
 // The one place that turns a kind number into a type: f is a generic callable and gets a ModelTag -- the model's struct, whether
 // its lookups use the wave's LDS tile, and how many one-wave blocks per CU the persistent grid of its trace launch has (interp:
 // 34 KiB of LDS per wave, 512 registers per lane: one wave per SIMD; scattered: 18.5 KiB, <= 256 registers: WAVES_PER_EU per
-// SIMD; ngo3d and simple3d: as Ngo, whose integrator fills the default WaveBudget whatever the density body needs).
+// SIMD; ngo3d, simple3d and at64thch: as Ngo, whose integrator fills the default WaveBudget whatever the density body needs).
 template <class M, bool LDS, int WAVES_PER_CU>
 struct ModelTag {
   using Model = M;
@@ -283,6 +291,7 @@ static int with_model(const srt_model *m, F &&f) {
   case KIND_SCATTERED: return f(ModelTag<ScatteredModel, true, 4 * ScatteredModel::WAVES_PER_EU>{});
   case KIND_NGO3D: return f(ModelTag<Ngo3dModel, false, 8>{});
   case KIND_SIMPLE3D: return f(ModelTag<Simple3dModel, false, 8>{});
+  case KIND_AT64THCH: return f(ModelTag<At64ThChModel, false, 8>{});
   }
   return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
 }
@@ -365,6 +374,39 @@ extern "C" int srt_model_trim(srt_model *m) {
   m->io.release();
   return SRT_OK;
 }
+// geopack's RECALC_08 for the handle's date: coefficients, GEO->GSM matrix, the adapters' PS and geopack's own PSI
+static int load_field_table(srt_model *m, const char *igrf_coeff_file) {
+  FieldConst &f = m->cm.fld;
+  std::string path;
+  if (igrf_coeff_file && *igrf_coeff_file) path = igrf_coeff_file;
+  else if (const char *e = getenv("SRT_IGRF_COEFFS")) path = e;
+  else { // the table shipped beside the library: <pkg>/lib/libsrt_hip.so -> <pkg>/data/igrf_coeffs.txt
+    Dl_info info;
+    if (dladdr((const void *)&srt_model_set_field, &info) && info.dli_fname) {
+      path = info.dli_fname;
+      size_t k = path.rfind('/');
+      path = (k == std::string::npos ? std::string(".") : path.substr(0, k)) + "/../data/igrf_coeffs.txt";
+    }
+  }
+  std::string err;
+  float G[105], H[105], REC[105];
+  if (!srt_host::igrf_setup(path.c_str(), f.yearday, f.msec, G, H, REC, f.A, &f.psi, err, &m->geopack_psi)) return srt_set_error(SRT_EIO, "%s", err.c_str());
+  igrf_pack_terms(G, H, REC, f);
+  m->have_table = true;
+  if (m->kind == KIND_AT64THCH) f.psi = 0.f; // the adapter's unset local (srt_at64thch.hpp, decision 2)
+  return SRT_OK;
+}
+// device copies of the handle's constants (and of modelnum 7's struct, which holds geopack's PSI)
+static int upload_constants(srt_model *m) {
+  HIP_OK(hipMemcpy(m->d_common.p, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
+  if (m->kind == KIND_AT64THCH) {
+    At64ThChModel &a = m->as<At64ThChModel>();
+    a.psi = m->geopack_psi;
+    a.fld = &m->d_common.p->fld;
+    HIP_OK(hipMemcpy(m->d_model.p, &a, sizeof a, hipMemcpyHostToDevice));
+  }
+  return SRT_OK;
+}
 // use_igrf (raytracer_driver.f95 --use_igrf; interp_dens_model_adapter.f95:236-241 and twins)
 extern "C" int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenko, const char *igrf_coeff_file) {
   if (!m) return srt_set_error(SRT_EINVAL, "null model");
@@ -374,27 +416,11 @@ extern "C" int srt_model_set_field(srt_model *m, int use_igrf, int use_tsyganenk
   int rc = ensure_model(m);
   if (rc) return rc;
   FieldConst &f = m->cm.fld;
-  if (use_igrf || use_tsyganenko) { // both need geopack's RECALC_08 for the date: coefficients, GEO->GSM matrix, dipole tilt
-    std::string path;
-    if (igrf_coeff_file && *igrf_coeff_file) path = igrf_coeff_file;
-    else if (const char *e = getenv("SRT_IGRF_COEFFS")) path = e;
-    else { // the table shipped beside the library: <pkg>/lib/libsrt_hip.so -> <pkg>/data/igrf_coeffs.txt
-      Dl_info info;
-      if (dladdr((const void *)&srt_model_set_field, &info) && info.dli_fname) {
-        path = info.dli_fname;
-        size_t k = path.rfind('/');
-        path = (k == std::string::npos ? std::string(".") : path.substr(0, k)) + "/../data/igrf_coeffs.txt";
-      }
-    }
-    std::string err;
-    float G[105], H[105], REC[105];
-    if (!srt_host::igrf_setup(path.c_str(), f.yearday, f.msec, G, H, REC, f.A, &f.psi, err)) return srt_set_error(SRT_EIO, "%s", err.c_str());
-    igrf_pack_terms(G, H, REC, f);
-  }
+  // both need geopack's RECALC_08 for the date: coefficients, GEO->GSM matrix, dipole tilt
+  if ((use_igrf || use_tsyganenko) && (rc = load_field_table(m, igrf_coeff_file))) return rc;
   f.use_igrf = use_igrf;
   f.use_tsy = use_tsyganenko;
-  HIP_OK(hipMemcpy(m->d_common.p, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
-  return SRT_OK;
+  return upload_constants(m);
 }
 // T04_s's PARMOD (driver flags --tsyganenko_Pdyn, _Dst, _ByIMF, _BzIMF, _W1 .. _W6; raytracer_driver.f95:292-341)
 extern "C" int srt_model_set_tsyganenko_params(srt_model *m, const double parmod[10]) {
@@ -403,8 +429,8 @@ extern "C" int srt_model_set_tsyganenko_params(srt_model *m, const double parmod
   int rc = ensure_model(m);
   if (rc) return rc;
   for (int i = 0; i < 10; ++i) m->cm.fld.parmod[i] = (float)parmod[i]; // real(parmod)
-  HIP_OK(hipMemcpy(m->d_common.p, &m->cm, sizeof(Common), hipMemcpyHostToDevice));
-  return SRT_OK;
+  m->have_parmod = true;
+  return upload_constants(m);
 }
 extern "C" int srt_model_kind(const srt_model *m) { return m ? m->kind : 0; }
 extern "C" int srt_model_nspec(const srt_model *m) { return m ? m->nspec : 0; }
@@ -523,6 +549,35 @@ extern "C" int srt_model_create_simple3d(double kp, int fixed_MLT, double MLT, i
   fill_common(m->cm, 4, qs, ms, yearday, msec);
   rc = model_finish(m);
   if (rc) {
+    srt_model_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return SRT_OK;
+}
+
+// ---- at64thch: closed form around one field-line trace per point (srt_at64thch.hpp, srt_fieldline.hpp) ----------
+extern "C" int srt_model_create_at64thch(int gcpm_kp, const double parmod[10], const char *igrf_coeff_file, int yearday, int msec,
+                                         srt_model **out) {
+  if (!out || !parmod) return srt_set_error(SRT_EINVAL, "null argument");
+  for (int i = 0; i < 10; ++i)
+    if (!std::isfinite(parmod[i])) return srt_set_error(SRT_EINVAL, "parmod must be finite");
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  srt_model *m = new srt_model;
+  m->kind = KIND_AT64THCH;
+  m->nspec = 3;
+  m->as<At64ThChModel>().gcpm_kp = gcpm_kp;
+  // the adapter's own species constants (:272-273): electrons, O+, H+
+  const double e_ = 1.602e-19;
+  double qs[3] = {e_ * -1.0, e_, e_};
+  double ms[3] = {9.10938188e-31, 16.0 * 1.6726e-27, 1.6726e-27};
+  fill_common(m->cm, 3, qs, ms, yearday, msec);
+  // the trace uses T04_s and IGRF whatever the field options say: the table and parmod are part of the model
+  for (int i = 0; i < 10; ++i) m->cm.fld.parmod[i] = (float)parmod[i]; // real(parmod), decision 1
+  m->have_parmod = true;
+  if ((rc = load_field_table(m, igrf_coeff_file)) || (rc = model_finish(m)) || (rc = upload_constants(m))) {
     srt_model_destroy(m);
     return rc;
   }
@@ -1041,6 +1096,46 @@ extern "C" int srt_dispersion(srt_model *m, int64_t n, const double *x, const do
   });
   if (rc) return rc;
   HIP_OK(hipMemcpy(out, dout.p, 10 * n * sizeof(double), hipMemcpyDeviceToHost));
+  return SRT_OK;
+}
+
+// TRACE_08, batched: one line per lane with the adapter's constants; out[n][6] = XF, YF, ZF, |IGRF| there, ending, points
+__global__ __launch_bounds__(64) void foot_kernel(const Common *__restrict__ cp, float psi, long long n, const double *x, double *out) {
+  const FieldConst &f = cp->fld;
+  const long long i = (long long)blockIdx.x * WAVE + threadIdx.x;
+  const long long j = i < n ? i : n - 1; // every lane takes part (the synthesis is wave-uniform)
+  const double px = x[3 * j], py = x[3 * j + 1], pz = x[3 * j + 2];
+  const float xg = (float)((px * f.cm - pz * f.sm) / R_E), yg = (float)(py / R_E), zg = (float)((pz * f.cm + px * f.sm) / R_E);
+  const fl::Foot ft = at64::foot_device(f, psi, at64::trace_const(), xg, yg, zg, true);
+  float bx, by, bz;
+  at64::igrf1_device(f, ft.x, ft.y, ft.z, bx, by, bz);
+  if (i < n) {
+#pragma clang fp contract(off)
+    double *o = out + 6 * i;
+    o[0] = ft.x;
+    o[1] = ft.y;
+    o[2] = ft.z;
+    o[3] = sqrtf(bx * bx + by * by + bz * bz);
+    o[4] = ft.kind;
+    o[5] = ft.npts;
+  }
+}
+extern "C" int srt_field_line_foot(srt_model *m, int64_t n, const double *x, double *out) {
+  if (!m || !x || !out || n < 0) return srt_set_error(SRT_EINVAL, "bad argument");
+  if (!m->have_table)
+    return srt_set_error(SRT_EINVAL, "srt_field_line_foot: the model has no IGRF coefficient table (srt_model_set_field with use_igrf "
+                                     "or use_tsyganenko loads it)");
+  if (!m->have_parmod)
+    return srt_set_error(SRT_EINVAL, "srt_field_line_foot: the model has no T04_s parameters (srt_model_set_tsyganenko_params)");
+  if (n == 0) return SRT_OK;
+  SRT_MODEL_SCOPE;
+  int rc = ensure_model(m);
+  if (rc) return rc;
+  DevBuf<double> dx, dout;
+  if ((rc = upload(dx, x, 3 * n))) return rc;
+  if (dout.alloc(6 * n) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+  launch_wave_blocks(foot_kernel, n, 0, (const Common *)m->d_common.p, m->geopack_psi, (long long)n, (const double *)dx.p, dout.p);
+  HIP_OK(hipMemcpy(out, dout.p, 6 * n * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
 }
 

@@ -121,10 +121,27 @@ static int make_model(int device, srt_model **out, double *del) {
     else get_real("MLT", mlt);
     p.del = 1.0e-6; // delDP (:1188)
     CHECK(srt_model_create_simple3d(kp, fixed_mlt, mlt, yearday, msec, &m));
+  } else if (modelnum == 7) {
+    // AT64ThCh_adapter (raytracer_driver.f95:1024-1136).  Required by name: gcpm_kp, an integer, and the ten T04_s parameters --
+    // also with --use_tsyganenko=0, because the model's field-line trace runs through T04_s + IGRF whatever the field options are.
+    double kpv = 0.0;
+    need(get_real("gcpm_kp", kpv), "gcpm_kp");
+    if (!(kpv == floor(kpv)) || fabs(kpv) > 1000.0) {
+      fprintf(stderr, "raytracer: --gcpm_kp must be an integer (the AT64ThCh adapter's gcpm_kp is one)\n");
+      exit(2);
+    }
+    const char *names[10] = {"tsyganenko_Pdyn", "tsyganenko_Dst", "tsyganenko_ByIMF", "tsyganenko_BzIMF", "tsyganenko_W1",
+                             "tsyganenko_W2",   "tsyganenko_W3",  "tsyganenko_W4",    "tsyganenko_W5",    "tsyganenko_W6"};
+    double parmod[10];
+    for (int k = 0; k < 10; ++k) need(get_real(names[k], parmod[k]), names[k]);
+    std::string coeffs;
+    getopt_named("igrf_coeffs", coeffs);
+    p.del = 1.0e-4; // delSP (:1189-1194)
+    CHECK(srt_model_create_at64thch((int)kpv, parmod, coeffs.empty() ? nullptr : coeffs.c_str(), yearday, msec, &m));
   } else {
-    fprintf(stderr, "raytracer: --modelnum=%d is not on the accelerated path (1, 3, 4 and 6 are; 5 = the 3-D Ngo model is in the "
-                    "library, srt_model_create_ngo3d, and not yet reachable from this executable; 2 = GCPM and 7 = AT64ThCh are "
-                    "out of scope)\n", modelnum);
+    fprintf(stderr, "raytracer: --modelnum=%d is not on the accelerated path (1, 3, 4 and 6 are, and 7 = AT64ThCh; 5 = the 3-D Ngo "
+                    "model is in the library, srt_model_create_ngo3d, and not yet reachable from this executable; 2 = GCPM is out "
+                    "of scope)\n", modelnum);
     return 2;
   }
   if (use_igrf != 0 || use_tsy != 0) {
@@ -152,7 +169,7 @@ int main(int argc, char **argv) {
          "  --dt0 --dtmax --tmax --root --fixedstep --maxerr --maxsteps --minalt\n"
          "  --inputraysfile --outputfile --outputper\n"
          "  --modelnum  (1) Ngo model  (3) interpolated model (gridded)  (4) interpolated model (scattered)\n"
-         "              (6) simplified GCPM (closed form)\n"
+         "              (6) simplified GCPM (closed form)  (7) AT64ThCh (one field-line trace per evaluated point)\n"
          "  model 1: --ngo_configfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1 --tsyganenko_Pdyn .. _W6\n"
          "  model 3: --interp_interpfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1\n"
          "  model 4: model 3 flags + --scattered_interp_window_scale --scattered_interp_order\n"
@@ -160,6 +177,9 @@ int main(int argc, char **argv) {
          "           [--scattered_interp_root_sample=N: record N of the file is the root of the reference's kd-tree (spacing 0)]\n"
          "  model 6: --kp --yearday --milliseconds_day [--fixed_MLT=1 --MLT=<hours>] --use_tsyganenko=0|1 --use_igrf=0|1\n"
          "           --tsyganenko_Pdyn .. _W6  (--ngo_configfile is accepted and ignored, as by the reference's driver)\n"
+         "  model 7: --gcpm_kp=<integer> --yearday --milliseconds_day --tsyganenko_Pdyn .. _W6 (all ten, also with\n"
+         "           --use_tsyganenko=0: the model's field-line trace always runs through T04_s + IGRF)\n"
+         "           --use_tsyganenko=0|1 --use_igrf=0|1 [--igrf_coeffs=<table>]\n"
          "  extra:   --device=N | --devices=0,1,..  --chunk_rays=N  --ray_order=0|1  --timing=1 (wall clock per phase)\n"
          "           --first_attempt_policy=1|0: error estimate of a ray's first adaptive attempt, where the reference reads an\n"
          "             unset variable: 1 (default) = from the k term alone, as the reference's gfortran build behaves;\n"

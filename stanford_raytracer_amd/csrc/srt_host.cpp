@@ -86,7 +86,7 @@ SunAngles sun_angles(int iyear, int iday, int ihour, int min, int isec) {
 } // namespace
 
 bool igrf_setup(const char *coeff_file, int yearday, int msec, float G[105], float H[105], float REC[105], float A[9],
-                float *psi, std::string &err) {
+                float *psi, std::string &err, float *geopack_psi) {
   // table: "g|h mn v1965 v1970 ... v2020 sv"
   static const int NEP = 12;
   std::vector<float> tg(13 * 105, 0.f), th(13 * 105, 0.f);
@@ -202,6 +202,10 @@ bool igrf_setup(const char *coeff_file, int yearday, int msec, float G[105], flo
     // sine of the dipole axis' colatitude (geopack2008.for:569), not RECALC_08's PSI (16th word).  The reference
     // therefore runs T04_s with PS = ST0 (~0.17 in 2010) whatever the date and hour; parity means doing the same.
     *psi = st0;
+  }
+  if (geopack_psi) { // geopack2008.for:1138-1142: PSI = ASIN(SPS), SPS = (DIP, EXGSW)
+    const float sps = dip1 * x1 + dip2 * x2 + dip3 * x3;
+    *geopack_psi = asinf(sps);
   }
   return true;
 }

@@ -61,6 +61,24 @@ module srt_bindc
        integer(c_int), value :: fixed_MLT, yearday, msec
        type(c_ptr) :: model
      end function srt_model_create_simple3d
+     ! modelnum = 7 (AT64ThCh_adapter.f95): one field-line trace through T04_s + IGRF per evaluated point; gcpm_kp is an integer,
+     ! parmod the ten --tsyganenko_* values (always needed); igrf_coeff_file: c_null_char = the table shipped with the library
+     integer(c_int) function srt_model_create_at64thch(gcpm_kp, parmod, igrf_coeff_file, yearday, msec, model) &
+          bind(C, name="srt_model_create_at64thch")
+       import :: c_int, c_char, c_ptr, c_double
+       integer(c_int), value :: gcpm_kp, yearday, msec
+       real(c_double), intent(in) :: parmod(10)
+       character(kind=c_char), intent(in) :: igrf_coeff_file(*)
+       type(c_ptr) :: model
+     end function srt_model_create_at64thch
+     ! geopack's TRACE_08, batched: x(3,n) SM metres -> out(6,n) = XF YF ZF (GSM, R_E), |IGRF| there, ending, number of points
+     integer(c_int) function srt_field_line_foot(model, n, x, out) bind(C, name="srt_field_line_foot")
+       import :: c_int, c_int64_t, c_ptr, c_double
+       type(c_ptr), value :: model
+       integer(c_int64_t), value :: n
+       real(c_double), intent(in) :: x(3,*)
+       real(c_double) :: out(6,*)
+     end function srt_field_line_foot
      integer(c_int) function srt_model_create_scattered_file(ptsfile, yearday, msec, window_scale, order, exact, &
           local_window_scale, model) bind(C, name="srt_model_create_scattered_file")
        import :: c_int, c_char, c_ptr, c_double

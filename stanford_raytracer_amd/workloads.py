@@ -99,6 +99,20 @@ def ngo3d_launch_set(nrays=None):
     return pos[:n], d[:n], w[:n]
 
 
+# modelnum 7 (AT64ThCh: one field-line trace per evaluated point): config[1]'s launch set and integrator settings again, Kp 4 and
+# the T04_s parameters of the goldens' first setting; del = the driver's delSP
+AT64THCH_100K = dict(rays=100_000, seed=2, gcpm_kp=4, yearday=2010001, msec=0,
+                     parmod=[4.0, 1.0, 0.0, -5.0, 0.132, 0.303, 0.083, 0.070, 0.211, 0.308],
+                     trace=dict(fixedstep=0, dt0=1e-3, dtmax=0.1, tmax=0.5, maxerr=5e-4, maxsteps=512, outputper=8, del_=1e-4))
+
+
+def at64thch_launch_set(nrays=None):
+    """The model-7 launch set: (pos0, dir0, w0) of AT64THCH_100K, or its first nrays rays."""
+    pos, d, w = launch_set(AT64THCH_100K["rays"], AT64THCH_100K["seed"])
+    n = AT64THCH_100K["rays"] if nrays is None else int(nrays)
+    return pos[:n], d[:n], w[:n]
+
+
 def appendix_b_rays(n=16):
     """The 16 probe rays of SURVEY.md Appendix B (explicit, non-field-aligned directions)."""
     rows = []
