@@ -79,24 +79,10 @@ SIMPLE3D_100K = dict(rays=100_000, seed=2, kp=4.0, yearday=2010001, msec=0, fixe
                      trace=dict(fixedstep=0, dt0=1e-3, dtmax=0.1, tmax=0.5, maxerr=5e-4, maxsteps=512, outputper=8, del_=1e-6))
 
 
-def simple3d_launch_set(nrays=None):
-    """The model-6 launch set: (pos0, dir0, w0) of SIMPLE3D_100K, or its first nrays rays."""
-    pos, d, w = launch_set(SIMPLE3D_100K["rays"], SIMPLE3D_100K["seed"])
-    n = SIMPLE3D_100K["rays"] if nrays is None else int(nrays)
-    return pos[:n], d[:n], w[:n]
-
-
 # modelnum 5 (the 3-D Ngo model): config[1]'s launch set and integrator settings again, the plasmapause file, Kp 4, MLT from each
 # point's longitude (all the reference's driver does); del = the driver's delDP
 NGO3D_100K = dict(rays=100_000, seed=2, newray=NEWRAY_PLASMAPAUSE, kp=4.0, yearday=2010001, msec=0, fixed_mlt=None,
                   trace=dict(fixedstep=0, dt0=1e-3, dtmax=0.1, tmax=0.5, maxerr=5e-4, maxsteps=512, outputper=8, del_=1e-6))
-
-
-def ngo3d_launch_set(nrays=None):
-    """The model-5 launch set: (pos0, dir0, w0) of NGO3D_100K, or its first nrays rays."""
-    pos, d, w = launch_set(NGO3D_100K["rays"], NGO3D_100K["seed"])
-    n = NGO3D_100K["rays"] if nrays is None else int(nrays)
-    return pos[:n], d[:n], w[:n]
 
 
 # modelnum 7 (AT64ThCh: one field-line trace per evaluated point): config[1]'s launch set and integrator settings again, Kp 4 and
@@ -106,10 +92,10 @@ AT64THCH_100K = dict(rays=100_000, seed=2, gcpm_kp=4, yearday=2010001, msec=0,
                      trace=dict(fixedstep=0, dt0=1e-3, dtmax=0.1, tmax=0.5, maxerr=5e-4, maxsteps=512, outputper=8, del_=1e-4))
 
 
-def at64thch_launch_set(nrays=None):
-    """The model-7 launch set: (pos0, dir0, w0) of AT64THCH_100K, or its first nrays rays."""
-    pos, d, w = launch_set(AT64THCH_100K["rays"], AT64THCH_100K["seed"])
-    n = AT64THCH_100K["rays"] if nrays is None else int(nrays)
+def model_launch_set(workload, nrays=None):
+    """The launch set of one of the *_100K workloads above: (pos0, dir0, w0) of its rays and seed, or its first nrays rays."""
+    pos, d, w = launch_set(workload["rays"], workload["seed"])
+    n = workload["rays"] if nrays is None else int(nrays)
     return pos[:n], d[:n], w[:n]
 
 

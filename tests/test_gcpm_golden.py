@@ -256,7 +256,7 @@ def test_gpu_interp_g1_g2_g3_on_the_gcpm_grid(gc, gpu_interp, oracle_interp):
 
 @gpu
 def test_gpu_interp_fixed_step_trajectories_on_the_gcpm_grid(gc, gpu_interp, oracle_interp):
-    from test_gpu_trace import LADDER, divergence, oracle_yardstick
+    from model_ladder import LADDER, divergence, oracle_yardstick
 
     tag = "g4_interp_fixed"
     ref_rows, ref_n, ref_stop = gc[tag + "_rows"], gc[tag + "_nrows"], gc[tag + "_stop"]
@@ -276,7 +276,7 @@ def test_gpu_interp_fixed_step_trajectories_on_the_gcpm_grid(gc, gpu_interp, ora
 
 @gpu
 def test_gpu_interp_adaptive_trajectories_on_the_gcpm_grid(gc, gpu_interp, oracle_interp):
-    from test_gpu_trace import curve_distance
+    from model_ladder import curve_distance
 
     tag = "g4_interp_adaptive"
     ref_rows, ref_n, ref_stop = gc[tag + "_rows"], gc[tag + "_nrows"], gc[tag + "_stop"]
@@ -334,7 +334,7 @@ def test_gpu_scattered_g0_on_the_gcpm_samples(gc, gpu_scattered, gcpm_pointsfile
 
 @gpu
 def test_gpu_scattered_gradients_and_trajectories_on_the_gcpm_samples(gc, gpu_scattered, gcpm_pointsfile):
-    from test_gpu_trajectory_stats import compare
+    from model_ladder import compare
 
     g = gpu_scattered
     o = oracle_scattered_like_reference(gc, gcpm_pointsfile, true_root=True)

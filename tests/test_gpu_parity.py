@@ -312,7 +312,7 @@ def test_scattered_trajectories(golden, gpu_models, oracle_scattered, pointsfile
     1e-9 shift of the launch points (the machinery of tests/test_gpu_trajectory_stats.py), not constants -- the oracle
     (with the reference's tree-root quirk, perm_seed = 2) is first held to the reference on the same rays."""
     from oracle import oracle
-    from test_gpu_trajectory_stats import compare
+    from model_ladder import compare
 
     rays, prm = golden["g4_scattered_rays"], golden["g4_scattered_launch_params"]
     ref_rows, ref_n, ref_stop = (golden["g4_scattered_launch_" + k] for k in ("rows", "nrows", "stop"))

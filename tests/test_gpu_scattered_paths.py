@@ -13,17 +13,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_DIR, vrel
+from scattered_paths import _own_list
 
 pytestmark = pytest.mark.gpu
-
-
-def _own_list(fn):
-    """Run fn() with the staging buffer switched off (own-list path for every stencil)."""
-    os.environ["SRT_SCATTERED_STAGING"] = "0"
-    try:
-        return fn()
-    finally:
-        del os.environ["SRT_SCATTERED_STAGING"]
 
 
 def _states(oracle_model, n, seed, scale=0.9):

@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_DIR, grad_errors, oracle_grad_sensitivity, oracle_step_sensitivity, vrel, within_sensitivity
-from test_gpu_scattered_paths import _own_list
+from scattered_paths import _own_list
 
 pytestmark = pytest.mark.gpu
 DEL = 1.0e-6

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import model_ladder as ladder
 from conftest import GOLDEN_DIR, vrel
 from stanford_raytracer_amd import workloads as wl
 
@@ -45,26 +46,13 @@ def test_model_kind_is_6(models):
 
 @pytest.mark.parametrize("tag", list(SETTINGS))
 def test_g0_plasma_params(gold, models, tag):
-    x, want, wantB, sens = (gold["g0_%s_%s" % (k, tag)] for k in ("x", "Ns", "B0", "sens"))
+    x, wantB = gold["g0_x_" + tag], gold["g0_B0_" + tag]
     g = models[tag].plasma_params(x)
-    err = np.max(np.abs(g[:, 4:8] - want) / want, axis=1)
-    bar = np.maximum(1e-11, 10.0 * sens)
     eB = vrel(g[:, 16:19], wantB)
-    print("G0 %s: %d points, density error max %.3g (bit-equal %.1f %%), B0 error max %.3g" % (tag, len(x), err.max(), 100 * np.mean(err == 0), eB.max()))
+    ladder.check_g0_density(g[:, 4:8], gold, tag, floor=1e-11, per_species=False, report=lambda err: print(
+        "G0 %s: %d points, density error max %.3g (bit-equal %.1f %%), B0 error max %.3g" % (tag, len(x), err.max(), 100 * np.mean(err == 0), eB.max())))
     assert np.all(np.isfinite(g[:, 4:8])) and np.all(g[:, 12:16] == 0)
-    assert np.all(err <= bar), "%d points over their bar, worst ratio %.3g" % ((err > bar).sum(), np.max(err / bar))
     assert eB.max() <= 2e-7
-
-
-def held(err, sens, bar):
-    """err / its bar, per sample: the ladder's bar, or 10 x the reference's own recorded sensitivity of that sample where that is
-    more (DESIGN section 4's sensitivity clause).  <= 1 means held."""
-    return err / np.maximum(bar, 10.0 * sens)
-
-
-def sens_rel(s, ref):
-    """recorded absolute sensitivity of a vector -> relative to the vector"""
-    return np.linalg.norm(s, axis=-1) / np.maximum(np.linalg.norm(ref, axis=-1), 1e-300)
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
@@ -75,158 +63,43 @@ def test_g1_dispersion_from_own_plasma_params(gold, models, tag):
 
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_g2_gradients_and_right_hand_side(gold, models, tag):
-    st, ref, sn = gold["g23_state_" + tag], gold["g2_" + tag], gold["g2_sens_" + tag]
-    g = models[tag].gradients(st[:, 0:3], st[:, 3:6], st[:, 6], DEL)
-    ek, sk = vrel(g[:, 0:3], ref[:, 0:3]), sens_rel(sn[:, 0:3], ref[:, 0:3])
-    ew, sw = np.abs(g[:, 3] - ref[:, 3]) / np.abs(ref[:, 3]), sn[:, 3] / np.abs(ref[:, 3])
-    ex, sx = vrel(g[:, 4:7], ref[:, 4:7]), sens_rel(sn[:, 4:7], ref[:, 4:7])
-    ev, sv = vrel(g[:, 7:10], ref[:, 7:10]), sens_rel(sn[:, 7:10], ref[:, 7:10])
-    ed, sd = vrel(g[:, 10:13], ref[:, 10:13]), sens_rel(sn[:, 10:13], ref[:, 10:13])
-    print("G2 %s: dFdk %.3g dFdw %.3g dFdx %.3g (reference's own %.3g) dx/dt %.3g dk/dt median %.3g max %.3g (own %.3g)"
-          % (tag, ek.max(), ew.max(), ex.max(), sx.max(), ev.max(), np.median(ed), ed.max(), sd.max()))
-    assert held(ek, sk, 1e-7).max() <= 1
-    assert held(ew, sw, 1e-6).max() <= 1
-    assert held(ex, sx, 1e-7).max() <= 1
-    assert held(ev, sv, 1e-6).max() <= 1
-    assert np.median(held(ed, sd, 1e-6)) <= 1 and held(ed, sd, 2e-5).max() <= 1
+    ladder.check_g2(models[tag], gold["g23_state_" + tag], gold["g2_" + tag], gold["g2_sens_" + tag], DEL, tag)
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_g3_single_steps(gold, models, tag):
-    st, ref, sn = gold["g23_state_" + tag], gold["g3_" + tag], gold["g3_sens_" + tag]
-    g = models[tag].rk_step(st, np.full(len(st), float(gold["g3_dt"])), DEL)
-    for o in (0, 7, 14):
-        ex, sx = vrel(g[:, o:o + 3], ref[:, o:o + 3]), sens_rel(sn[:, o:o + 3], ref[:, o:o + 3])
-        ek, sk = vrel(g[:, o + 3:o + 6], ref[:, o + 3:o + 6]), sens_rel(sn[:, o + 3:o + 6], ref[:, o + 3:o + 6])
-        print("G3 %s out %d: position median %.3g max %.3g (own %.3g), k median %.3g max %.3g (own %.3g)"
-              % (tag, o // 7, np.median(ex), ex.max(), sx.max(), np.median(ek), ek.max(), sk.max()))
-        assert np.median(held(ex, sx, 1e-8)) <= 1 and held(ex, sx, 1e-7).max() <= 1, (np.sort(held(ex, sx, 1e-7))[-3:], np.median(held(ex, sx, 1e-8)))
-        assert np.median(held(ek, sk, 1e-7)) <= 1 and held(ek, sk, 1e-2).max() <= 1
-        assert np.array_equal(g[:, o + 6], st[:, 6])  # omega is carried unchanged
+    ladder.check_g3(models[tag], gold["g23_state_" + tag], gold["g3_" + tag], gold["g3_sens_" + tag], gold["g3_dt"], DEL, tag)
 
 
-def run_params(gold, mode):
-    from stanford_raytracer_amd import api
-    fixedstep, dt0, dtmax, tmax, maxerr, maxsteps, minalt, del_ = gold["run_%s_params" % mode]
-    return api.make_params(dt0=dt0, dtmax=dtmax, tmax=tmax, maxerr=maxerr, maxsteps=int(maxsteps), minalt=minalt,
-                           fixedstep=int(fixedstep), del_=del_, outputper=1), float(tmax)
-
-
-def trace_golden_rays(gold, models, mode, pos0=None):
+def golden_launches(models):
     """The 64 golden rays: the first 32 in setting a (free MLT), the others in setting b (fixed MLT)."""
-    p, _ = run_params(gold, mode)
-    pos0 = gold["run_pos0"] if pos0 is None else pos0
-    d, w = gold["run_dir0"], gold["run_w0"]
-    out = [models[t].trace(pos0[h], d[h], w[h], params=p)[:3] for t, h in (("a", slice(0, 32)), ("b", slice(32, 64)))]
-    return tuple(np.concatenate([o[k] for o in out]) for k in range(3))
-
-
-def widen(rows7):
-    """golden rows (t, pos, vgrel) -> the library's 20-column layout (only those columns filled)"""
-    r = np.full(rows7.shape[:2] + (20,), np.nan)
-    r[:, :, 0:4] = rows7[:, :, 0:4]
-    r[:, :, 7:10] = rows7[:, :, 4:7]
-    return r
+    return [(models["a"], slice(0, 32)), (models["b"], slice(32, 64))]
 
 
 def test_g4_fixed_step_trajectories(gold, models):
-    rows, nrows, stop = trace_golden_rays(gold, models, "fixed")
-    ref, rn, rs = gold["run_fixed_rows"], gold["run_fixed_nrows"], gold["run_fixed_stop"]
-    sh, shn, shs = gold["run_fixed_shift_rows"], gold["run_fixed_shift_nrows"], gold["run_fixed_shift_stop"]
-    steady = (rn == shn) & (rs == shs)      # rays whose fate the reference itself keeps under its 1e-9 shift
-    assert steady.sum() >= 56
-    assert np.array_equal(nrows[steady], rn[steady]) and np.array_equal(stop[steady], rs[steady])
-    worst = 0.0
-    for i in np.nonzero(steady & (rn > 1))[0]:
-        T = rn[i]
-        assert np.array_equal(rows[i, 0, 1:4], ref[i, 0, 1:4])
-        e = vrel(rows[i, :T, 1:4], ref[i, :T, 1:4]).max()
-        own = vrel(sh[i, :T, 1:4], ref[i, :T, 1:4]).max()
-        bar = 10.0 * max(own, 1e-8)             # floor: the G3 median bar
-        worst = max(worst, e / bar)
-        assert e <= bar, (i, e, own)
-        assert np.allclose(rows[i, :T, 0], ref[i, :T, 0], rtol=1e-14, atol=0)
-    print("G4 fixed: worst error / bar = %.3g" % worst)
+    ladder.check_g4_fixed(ladder.trace_golden_rays(gold, golden_launches(models), "fixed"), gold, min_steady=56)
 
 
 def test_g4_adaptive_trajectories(gold, models):
-    from test_gpu_trajectory_stats import compare
-    _, tmax = run_params(gold, "adaptive")
-    mine_run = trace_golden_rays(gold, models, "adaptive")
-    ref = (widen(gold["run_adaptive_rows"]), gold["run_adaptive_nrows"], gold["run_adaptive_stop"])
-    sh = (widen(gold["run_adaptive_shift_rows"]), gold["run_adaptive_shift_nrows"], gold["run_adaptive_shift_stop"])
-    cap = ref[0].shape[1]
-    mine = compare((mine_run[0][:, :cap], mine_run[1], mine_run[2]), ref, tmax)
-    yard = compare(sh, ref, tmax)
-    msg = "\nGPU vs reference: %s\nreference vs reference (launch shifted 1e-9): %s\ncurve ratio: median %.2f p90 %.2f" % (
-        mine, yard, mine["curve_median"] / yard["curve_median"], mine["curve_p90"] / yard["curve_p90"])
-    print(msg)
-    n = len(ref[1])
-    assert mine["n_curves"] >= 48
-    both = (mine_run[1] > 1) & (ref[1] > 1)
-    assert np.array_equal(mine_run[0][both, 0, 1:4], ref[0][both, 0, 1:4])
-    # curves: no further from the reference than 2 x the reference is from itself (floors: the survey ladder's, as for the
-    # other models' adaptive trajectories)
-    assert mine["curve_median"] <= 2 * max(yard["curve_median"], 7e-8), msg
-    assert mine["curve_p90"] <= 2 * max(yard["curve_p90"], 4e-5), msg
-    # decisions: stop codes and row counts
-    assert mine["stop_agree"] >= yard["stop_agree"] - 1.5 / n, msg
-    assert mine["same_t"] >= yard["same_t"] - 2.5 / n, msg
-    assert mine["rows_rel"] <= max(2 * yard["rows_rel"], 0.02), msg
+    ladder.check_g4_adaptive(ladder.trace_golden_rays(gold, golden_launches(models), "adaptive"), gold, min_curves=48, same_t=ladder.same_t_first_rows)
 
 
 def test_a_ray_on_the_z_axis_stops_and_leaves_its_neighbours_alone(gold, models):
     """On the z axis cos(latitude) is 6e-17 and L is 1e33 or infinite: the ray must end with a stop code of its own, and the
     other 63 lanes of its wave must produce the rows they produce without it."""
-    p, _ = run_params(gold, "adaptive")
-    pos0, d, w = gold["run_pos0"].copy(), gold["run_dir0"], gold["run_w0"]
-    base = models["a"].trace(pos0, d, w, params=p)
-    k = 5
-    pos0[k] = [0.0, 0.0, 2.0 * wl.R_E]
-    rows, nrows, stop, _ = models["a"].trace(pos0, d, w, params=p)
-    assert stop[k] != 0 and 1 <= nrows[k] <= int(gold["run_adaptive_params"][5])
-    others = np.arange(len(w)) != k
-    assert np.array_equal(nrows[others], base[1][others]) and np.array_equal(stop[others], base[2][others])
-    assert np.array_equal(np.nan_to_num(rows[others]), np.nan_to_num(base[0][others]))
-    # the density there is what the layered entry point gives for the same point: finite or not, never a fault
-    g = models["a"].plasma_params(pos0[k:k + 1])
-    assert g.shape == (1, 19)
+    assert ladder.z_axis_ray(gold, models["a"]) != 0
 
 
 NX, NY, NZ = 6, 5, 4
-BOUNDS = np.array([1.3, 4.5, -2.0, 2.5, -1.5, 1.8]) * wl.R_E
 
 
 @pytest.mark.parametrize("compder", [0, 1])
 def test_grid_built_from_the_handle(models, compder):
-    g = models["a"]
-    F, D = g.build_grid(NX, NY, NZ, BOUNDS, compder=bool(compder))
-    x = np.arange(NX) * ((BOUNDS[1] - BOUNDS[0]) / (NX - 1.0)) + BOUNDS[0]
-    y = np.arange(NY) * ((BOUNDS[3] - BOUNDS[2]) / (NY - 1.0)) + BOUNDS[2]
-    z = np.arange(NZ) * ((BOUNDS[5] - BOUNDS[4]) / (NZ - 1.0)) + BOUNDS[4]
-    Z, Y, X = np.meshgrid(z, y, x, indexing="ij")
-    P = np.stack([X, Y, Z], axis=-1)
-    mine = np.log(g.plasma_params(P.reshape(-1, 3))[:, 4:8]).reshape(F.shape)
-    assert np.all(np.isfinite(F))
-    assert np.abs(F - mine).max() <= 2e-14        # device log vs host log of the same densities
-    assert (D is None) == (not compder)
-    if compder:
-        assert len(D) == 7 and all(np.all(np.isfinite(b)) for b in D)
-    # the model-3 handle made from it traces
-    t = g.to_interp(NX, NY, NZ, BOUNDS, compder=bool(compder))
-    assert t.kind == 3
-    pos, d, w = wl.launch_set(64, 11)
-    rows, nrows, stop, steps = t.trace(pos * 0.5, d, w, fixedstep=1, dt0=1e-3, dtmax=0.1, tmax=0.01, maxerr=5e-4, maxsteps=8, del_=1e-6)
-    assert steps > 0 and set(np.unique(stop).tolist()) <= {0, 1, 2, 3, 5, 6, 9}
-    at_nodes = t.plasma_params(P.reshape(-1, 3))[:, 4:8]
-    assert np.abs(np.log(at_nodes) - F.reshape(-1, 4)).max() <= 1e-12 * np.abs(F).max()
+    ladder.check_grid_from_handle(models["a"], NX, NY, NZ, ladder.BOUNDS, compder=bool(compder), nspec=4, then_trace=True)
 
 
 def test_sample_builder_accepts_the_handle(models):
-    rec, counts = models["a"].build_samples(BOUNDS, n_initial_uniform=200, seed=3)
-    assert rec.shape == (200, 7) and counts[2] == 200
-    want = np.log(models["a"].plasma_params(rec[:, 0:3])[:, 4:8])
-    assert np.abs(rec[:, 3:7] - want).max() <= 2e-14
+    ladder.check_sample_builder(models["a"])
 
 
 def test_hoisting_is_exact(gold, models):

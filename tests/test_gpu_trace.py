@@ -12,27 +12,10 @@ import numpy as np
 import pytest
 
 from conftest import DELS, vrel
+from model_ladder import LADDER, curve_distance, divergence, oracle_yardstick
 from stanford_raytracer_amd import workloads as wl
 
 pytestmark = pytest.mark.gpu
-LADDER = {1: 1.2e-10, 10: 7e-8, 100: 4e-5}
-
-
-def divergence(ra, na, rb, nb, r, cols):
-    sel = (na > r) & (nb > r)
-    if not sel.any():
-        return 0.0
-    return float(vrel(ra[sel, r][:, cols], rb[sel, r][:, cols]).max())
-
-
-def oracle_yardstick(om, rays, kw, rows_at, cap):
-    base = om.trace(rays[:, :3], rays[:, 3:6], rays[:, 6], capacity=cap, **kw)
-    out = {r: 0.0 for r in rows_at}
-    for eps in (1e-9, -1e-9):
-        pert = om.trace(rays[:, :3] * (1 + eps), rays[:, 3:6], rays[:, 6], capacity=cap, **kw)
-        for r in rows_at:
-            out[r] = max(out[r], divergence(pert[0], pert[1], base[0], base[1], r, slice(1, 4)))
-    return base, out
 
 
 @pytest.mark.parametrize("name,tag,rows_at", [("ngo", "g4_ngo_fixed", (1, 10, 100)), ("interp", "g4_interp_fixed", (1, 10, 50))])
@@ -58,34 +41,6 @@ def test_fixed_step_trajectories(golden, gpu_models, oracle_models, name, tag, r
         bound = 10 * max(yard[r], LADDER.get(r, 4e-5))
         assert d <= bound, "row %d: position divergence %.2e > %.2e" % (r, d, bound)
         assert np.allclose(rows[:, r, 0], ref_rows[:, r, 0], rtol=1e-12)  # same time grid
-
-
-C_LIGHT = 299792458.0
-
-
-def hermite(tt, t, y, v):
-    """Cubic Hermite resampling of a trajectory (positions y, velocities v at knots t) at times tt."""
-    idx = np.clip(np.searchsorted(t, tt, side="right") - 1, 0, len(t) - 2)
-    h = t[idx + 1] - t[idx]
-    u = (tt - t[idx]) / h
-    h00, h10, h01, h11 = 2 * u**3 - 3 * u**2 + 1, u**3 - 2 * u**2 + u, -2 * u**3 + 3 * u**2, u**3 - u**2
-    return (h00[:, None] * y[idx] + (h10 * h)[:, None] * v[idx] + h01[:, None] * y[idx + 1] + (h11 * h)[:, None] * v[idx + 1])
-
-
-def curve_distance(rows_a, n_a, rows_b, n_b, tmax):
-    """max over rays of the relative distance between the two position curves on a common time grid.
-    Adaptive runs place their knots differently, so both curves are resampled with cubic Hermite
-    interpolation using the group velocity (vgrel * c) the rows carry."""
-    worst = 0.0
-    for i in range(rows_a.shape[0]):
-        ta, tb = rows_a[i, :n_a[i], 0], rows_b[i, :n_b[i], 0]
-        if len(ta) < 3 or len(tb) < 3:
-            continue
-        tt = np.linspace(0, min(ta[-1], tb[-1], tmax), 20)
-        pa = hermite(tt, ta, rows_a[i, :n_a[i], 1:4], rows_a[i, :n_a[i], 7:10] * C_LIGHT)
-        pb = hermite(tt, tb, rows_b[i, :n_b[i], 1:4], rows_b[i, :n_b[i], 7:10] * C_LIGHT)
-        worst = max(worst, float(vrel(pa, pb).max()))
-    return worst
 
 
 @pytest.mark.parametrize("name,tag", [("ngo", "g4_ngo_adaptive"), ("ngoducts", "g4_ngoducts_adaptive"),

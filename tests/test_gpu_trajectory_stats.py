@@ -16,46 +16,12 @@ import os
 import numpy as np
 import pytest
 
-from conftest import DELS, vrel
+from conftest import DELS
+from model_ladder import compare
 from stanford_raytracer_amd import workloads as wl
 
 pytestmark = pytest.mark.gpu
-C_LIGHT = 299792458.0
 NTH = max(1, min(16, os.cpu_count() or 1))
-
-
-def hermite(tt, t, y, v):
-    idx = np.clip(np.searchsorted(t, tt, side="right") - 1, 0, len(t) - 2)
-    h = t[idx + 1] - t[idx]
-    u = (tt - t[idx]) / h
-    h00, h10, h01, h11 = 2 * u**3 - 3 * u**2 + 1, u**3 - 2 * u**2 + u, -2 * u**3 + 3 * u**2, u**3 - u**2
-    return h00[:, None] * y[idx] + (h10 * h)[:, None] * v[idx] + h01[:, None] * y[idx + 1] + (h11 * h)[:, None] * v[idx + 1]
-
-
-def curve_distances(ra, na, rb, nb, tmax):
-    """per ray: max relative distance between the two position curves on a common time grid (NaN: too short)."""
-    out = np.full(ra.shape[0], np.nan)
-    for i in range(ra.shape[0]):
-        ta, tb = ra[i, :na[i], 0], rb[i, :nb[i], 0]
-        if len(ta) < 3 or len(tb) < 3:
-            continue
-        tt = np.linspace(0, min(ta[-1], tb[-1], tmax), 20)
-        pa = hermite(tt, ta, ra[i, :na[i], 1:4], ra[i, :na[i], 7:10] * C_LIGHT)
-        pb = hermite(tt, tb, rb[i, :nb[i], 1:4], rb[i, :nb[i], 7:10] * C_LIGHT)
-        out[i] = float(vrel(pa, pb).max())
-    return out
-
-
-def compare(a, b, tmax):
-    """statistics of run a against run b (each = rows, nrows, stop)."""
-    (ra, na, sa), (rb, nb, sb) = a, b
-    d = curve_distances(ra, na, rb, nb, tmax)
-    d = d[np.isfinite(d)]
-    both = (na > 4) & (nb > 4)
-    same_t = np.all(ra[both, 1:4, 0] == rb[both, 1:4, 0], axis=1)
-    return {"curve_median": float(np.median(d)), "curve_p90": float(np.percentile(d, 90)), "curve_p99": float(np.percentile(d, 99)),
-            "stop_agree": float(np.mean(sa == sb)), "same_t": float(same_t.mean()), "n_curves": int(len(d)),
-            "rows_rel": abs(int(na.sum()) - int(nb.sum())) / max(int(nb.sum()), 1)}
 
 
 CASES = {"ngo": dict(n=1024, scale=1.0, tmax=0.2, maxsteps=120), "interp": dict(n=1024, scale=0.9, tmax=0.2, maxsteps=120),

@@ -25,8 +25,8 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_ring_residency_layout import (HOLDS_FIRST, HOLDS_LAST, INVALID, MAX_IMM, PAD, RES_END, RING, UNIT,  # noqa: E402
-                                        WAVE, prepare, read_unit)
+from ring_residency_model import (HOLDS_FIRST, HOLDS_LAST, INVALID, MAX_IMM, PAD, RES_END, RING, UNIT,  # noqa: E402
+                                  WAVE, prepare, read_unit)
 
 UNDEFINED = ("in flight",)
 

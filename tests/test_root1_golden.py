@@ -107,7 +107,7 @@ def test_gpu_fixed_step_root1(g1, gpu_models, oracle_models, name, tag, rows_at)
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,tag", [("ngo", "ngo_adaptive_root1"), ("interp", "interp_adaptive_root1")])
 def test_gpu_adaptive_root1(g1, gpu_models, oracle_models, name, tag):
-    from test_gpu_trace import curve_distance
+    from model_ladder import curve_distance
 
     rays, prm = g1["hf_rays"], g1[tag + "_params"]
     ref_rows, ref_n, ref_stop = g1[tag + "_rows"], g1[tag + "_nrows"], g1[tag + "_stop"]
