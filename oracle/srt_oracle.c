@@ -917,7 +917,12 @@ int so_is_right_handed(double n2, double phi, double S, double D, double P) {
   sym3_eigenvalues(a, Dm, b, c, d, ev);
   double lam = ev[0];
   if (fabs(ev[1]) < fabs(lam)) lam = ev[1];
-  if (fabs(ev[2]) < fabs(lam)) lam = ev[2];
+  /* b == 0 (phi exactly 0): z decouples, no rotation touches ev[2] = d.  Where d is the least eigenvalue E = (0, 0, 1), both
+   * atan2(0, 0) are 0 and the reference answers "right-handed" whatever D is. */
+  if (fabs(ev[2]) < fabs(lam)) {
+    if (b == 0.0) return 1;
+    lam = ev[2];
+  }
   return !(Dm / (c - lam) > 0.0);
 }
 
@@ -929,7 +934,9 @@ void so_solve_dispersion_relation(so_model *m, const double k[3], double w, cons
   so_plasma_params(m, x, qs, Ns, ms, nus, B0);
   double cos2phi = (dot3(k, B0) * dot3(k, B0)) / (dot3(k, k) * dot3(B0, B0));
   double sin2phi = 1.0 - cos2phi;
-  double phi = acos(sqrt(cos2phi)) * R2D;
+  /* k along B0: cos2phi can round above 1, where the reference stops on the NaN (Appendix A-2).  Clamped for phi only, as
+   * the device does; nothing changes where the reference survives. */
+  double phi = acos(sqrt(cos2phi > 1.0 ? 1.0 : cos2phi)) * R2D;
   double B0mag = sqrt(dot3(B0, B0));
   double S, D, P, R, L;
   so_stix_parameters(w, m->nspec, qs, Ns, ms, B0mag, &S, &D, &P, &R, &L);

@@ -528,7 +528,7 @@ __device__ inline bool is_right_handed(double n2, double phi_deg, double S, doub
   double a11 = (double)(float)(S - n2);
   double a12 = 0.0;
   double a22 = (double)(float)(P - n2 * (sp * sp));
-  const double c = a11, Dm = a01;
+  const double c = a11, Dm = a01, b = a02;
 #pragma unroll 1
   for (int sweep = 0; sweep < 8; ++sweep) {
     jacobi_rot(a00, a11, a01, a02, a12); // (p,q)=(0,1), r=2
@@ -537,8 +537,14 @@ __device__ inline bool is_right_handed(double n2, double phi_deg, double S, doub
   }
   double lam = a00;
   if (fabs(a11) < fabs(lam)) lam = a11;
-  if (fabs(a22) < fabs(lam)) lam = a22;
-  return !(Dm / (c - lam) > 0.0);
+  // b == 0 (phi exactly 0): z decouples, no rotation touches a22.  Where it is the least eigenvalue E = (0, 0, 1), both
+  // atan2(0, 0) of the reference are 0 and its answer is "right-handed" whatever D is.
+  bool zvec = false;
+  if (fabs(a22) < fabs(lam)) {
+    lam = a22;
+    zvec = (b == 0.0);
+  }
+  return zvec || !(Dm / (c - lam) > 0.0);
 }
 
 // solve_dispersion_relation (raytracer.f95:408-502): complex roots k1, k2 (re, im) along direction k.
