@@ -140,9 +140,6 @@ __device__ __forceinline__ void igrf_core(const FieldConst &f, const float (&xg)
     kmax = o > kmax ? o : kmax;
   }
   kmax = __builtin_amdgcn_readfirstlane(kmax);
-#ifdef SRT_IGRF_PROBE_KMAX
-  kmax = kmax < SRT_IGRF_PROBE_KMAX ? kmax : SRT_IGRF_PROBE_KMAX; // (timing probe only: wrong fields)
-#endif
   // The points of one stencil lie within 1e-6 of each other: they share the truncation degree unless r + 2 crosses an
   // integer between them.  Then ONE predicate per lane and trip covers all NP chains (the per-point form below costs
   // an exec-mask save/restore per point and trip).

@@ -65,6 +65,7 @@ __device__ __forceinline__ double sqrt_pos(double x) {
 }
 // g = sqrt(x) and inv = 1 / g for a positive normal x from ONE v_rsq_f64: the Goldschmidt pair (g, h = 1 / (2 g)) of sqrt_pos,
 // then one Newton step on 2 h against the finished g (<= 1 ulp each; 13 operations against sqrt_pos + fdiv's 20)
+// (no caller in the kernels -- chol_y measured no faster with it, HISTORY section 12.1; the host and GPU fastmath tests call it directly)
 __device__ __forceinline__ void sqrt_and_inv_pos(double x, double &g_out, double &inv_out) {
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;

@@ -100,15 +100,10 @@ __device__ __noinline__ double offset_F(const CM &cm, double px, double py, doub
 // Models whose launches end in a long tail of a few rays (config[1]: 27 of 100 k rays run to maxsteps, the mean ray stops
 // after 29 steps) spread the six offset evaluations of a right-hand side over idle lanes when at most 8 lanes of the wave
 // carry a ray: the launch then runs at one ray's sequential trip time, and those six chains in a row were a quarter of it.
-#ifndef SRT_NGO_SPREAD
-#define SRT_NGO_SPREAD 1 // (0: every right-hand side in the ray's own lane, for A/B)
-#endif
-#ifndef SRT_INTERP_SPREAD
-#define SRT_INTERP_SPREAD 0 // (1: the same for the interp model's tail -- measured, HISTORY section 12.3)
-#endif
+// (The same spread for the interp model's tail was measured 9 % slower in the bulk: HISTORY section 12.3.)
 template <class M>
 constexpr bool spread_rhs() {
-  return (SRT_NGO_SPREAD != 0 && (std::is_same<M, NgoModel>::value || std::is_same<M, Ngo3dModel>::value)) || (SRT_INTERP_SPREAD != 0 && std::is_same<M, InterpModel>::value);
+  return std::is_same<M, NgoModel>::value || std::is_same<M, Ngo3dModel>::value;
 }
 // the exchange area of the spread right-hand sides: ONE allocation per kernel, whichever call sites use it
 struct SpreadLds {

@@ -561,26 +561,6 @@ struct ScatteredModel {
   static constexpr int LDS_SCRATCH_SLOT = LIST_DOUBLES, LDS_BLOCK_SLOT = LDS_SCRATCH_SLOT + 1, LDS_PARK = LDS_SCRATCH_SLOT + 2,
                        LDS_PHASE = LDS_PARK + 32, LDS_HDR = LDS_SCRATCH_SLOT + 64;
   static constexpr int LDS_DOUBLES = LDS_HDR + 4 * 64;
-#ifndef SRT_SCAT_TAYLOR
-// 1 (round 4): the seven windows of a sample in pass 1 as a cubic in the angle difference about the centre's window (instead of cos / sin
-// series of the difference and the addition theorem), and -- for a stencil all of whose samples are far enough -- the seven weights
-// from a second-order expansion of the weight about the centre (sf_weights); 0: round 3's series everywhere.
-#define SRT_SCAT_TAYLOR 1
-#endif
-#ifndef SRT_SCAT_REC_AHEAD
-// 1: the weights pass reads the staging records of the samples beyond the LDS side arrays one trip ahead (second-order tier)
-#define SRT_SCAT_REC_AHEAD 1
-#endif
-#ifndef SRT_SCAT_FUSED
-// 1: the weights and the pair loop of the shared path run FUSED, tile by tile (sf_fused): the 64 records of a tile --
-// {x, y, z, ln N_s, the eight half-weights} -- exist only in LDS, between the lanes that weigh them (lane = sample) and the
-// groups that sum them (lane = (point, 1 of 8)).  Nothing of a record goes to device memory any more except {r_c, cos, sin} of
-// the samples beyond the LDS side arrays; the sample itself is gathered twice (pass 1, fused pass) from the sample array.
-// 0 (default until measured faster): the three-phase form with the staging records written twice and read back through the LDS-DMA ring.
-#define SRT_SCAT_FUSED 0
-#endif
-  static constexpr bool FUSED = SRT_SCAT_FUSED != 0;
-  static constexpr int TILE_BYTES = 8192; // 64 records x 128 B, [16-byte chunk][record], at the END of the list area
   // candidate block of a lane: BLOCK_CAP entries {float dx, dy, dz (from the block's centre), int sample index}
   static constexpr int BLOCK_CAP = 4096, BLOCK_DOUBLES = 64 * BLOCK_CAP * 2;
   static constexpr int TRIP_MAX = 9 * 64; // entries one trip of a 27-cell scan can add
@@ -709,12 +689,7 @@ struct ScatteredModel {
 #pragma unroll
       for (int l = 0; l < j; ++l) s -= at(l, j) * at(l, j);
       if (!(s > 0.0)) return 1;
-#ifdef SRT_SCAT_RSQ
-      double ujj, inv; // (a positive pivot of sums of squares of O(1) offsets: normal range)
-      fm::sqrt_and_inv_pos(s, ujj, inv);
-#else
       const double ujj = fm::sqrt_pos(s), inv = fdiv(1.0, ujj); // (a positive pivot of sums of squares of O(1) offsets: normal range)
-#endif
       at(j, j) = ujj;
       rinv[j] = inv;
 #pragma unroll
@@ -871,26 +846,6 @@ struct ScatteredModel {
     S.c = S.b + S.cap;
     return S;
   }
-  // The fused form: the list area is [list | {cos, sin} of cap samples | r_c of cap samples | .. | tile]; x, y, z come with the
-  // sample's second gather.  A shared list must leave the tile its 8 KiB: FUSED_LIST_CAP entries at most.
-  struct Side2 {
-    SRT_LDS d2_t *cs;
-    SRT_LDS double *rc;
-    int cap;
-  };
-  static constexpr int FUSED_LIST_CAP = (LIST_DOUBLES * 8 - TILE_BYTES) / 4 - 64;
-  __device__ __forceinline__ static Side2 side2_of(SRT_LDS const int *list, int n_list) {
-    const int used = (n_list + 3) >> 2; // 16-byte units the list occupies
-    Side2 S;
-    const int room = LIST_DOUBLES * 8 - TILE_BYTES - used * 16;
-    S.cap = room > 0 ? room / 24 : 0;
-    S.cs = (SRT_LDS d2_t *)const_cast<SRT_LDS int *>(list) + used;
-    S.rc = (SRT_LDS double *)(S.cs + S.cap);
-    return S;
-  }
-  __device__ __forceinline__ static SRT_LDS char *tile_of(SRT_LDS const int *list) {
-    return (SRT_LDS char *)const_cast<SRT_LDS int *>(list) + (LIST_DOUBLES * 8 - TILE_BYTES);
-  }
   // p7near: the free point 7 lies as close to the centre as the six offset points may (<= 1e-3 radius) and takes the
   // addition theorem / the series like them; else its window is evaluated by cos() and its weight by etainv().
   __device__ __forceinline__ void sf_pass1(const double (&p_in)[3], unsigned long long livemask, int npts, int n_list,
@@ -919,7 +874,6 @@ struct ScatteredModel {
 #pragma unroll
     for (int gg = 0; gg < 8; ++gg) lv8[gg] = (livemask >> (8 * gg)) & 1ull; // wave-uniform
     const Side side = side_of(list, n_list);
-    const Side2 side2 = side2_of(list, n_list);
     // the points' offsets from the centre (as in sf_weights)
     const double reps = radius * 5.0e-16;
     const double da3[3] = {pg[1][0] - pg[0][0], pg[3][1] - pg[0][1], pg[5][2] - pg[0][2]};
@@ -967,7 +921,7 @@ struct ScatteredModel {
 #define SF_ROW(dst, expr)                                                                                              \
   _Pragma("unroll") for (int j = 0; j < NQ; ++j) dst[j] = expr;                                                        \
   _Pragma("unroll") for (int j = 0; j < NQ; ++j) asm volatile("" : "+v"(dst[j]))
-        double t[NQ], tin[NQ], eps[NQ], pl[NQ], da[NQ], y[NQ], h[NQ], r[NQ];
+        double t[NQ], tin[NQ], eps[NQ], pl[NQ], da[NQ], h[NQ];
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
           if (j < 6) {
@@ -981,13 +935,7 @@ struct ScatteredModel {
           }
         }
         SF_ROW(eps, t[j] * inv2);
-        if constexpr (SRT_SCAT_TAYLOR != 0) { // (to eps^2: the next term, 5 eps^3 / 64 <= 6e-10 of an angle difference <= 3e-3)
-          SF_ROW(pl, fma(eps[j], 0.125, -0.25));
-        } else {
-          SF_ROW(pl, fma(eps[j], 0.0546875, -0.078125));
-          SF_ROW(pl, fma(eps[j], pl[j], 0.125));
-          SF_ROW(pl, fma(eps[j], pl[j], -0.25));
-        }
+        SF_ROW(pl, fma(eps[j], 0.125, -0.25)); // (to eps^2: the next term, 5 eps^3 / 64 <= 6e-10 of an angle difference <= 3e-3)
         SF_ROW(pl, fma(eps[j], pl[j], 1.0));
         SF_ROW(da, t[j] * hinv);
         SF_ROW(da, da[j] * pl[j]);
@@ -1000,25 +948,13 @@ struct ScatteredModel {
             da[j] = (fm::sqrt_pos(tin[j]) - rc) * pi_R;
           }
         }
-        if constexpr (SRT_SCAT_TAYLOR != 0) {
-          // the window W(a) = 1/2 + cos(a)/2 at a_c + da as a cubic in da about a_c: derivatives -sin/2, -cos/2, +sin/2;
-          // |da| <= pi 1e-3 (the free point; 1e-5 for the six offset points): remainder da^4 / 48 <= 2e-12 (1e-21) --
-          // 3 rows instead of 9
-          const double w1 = -0.5 * sa, w2 = -0.25 * ca, w3 = (1.0 / 12.0) * sa, w0c = 0.5 + 0.5 * ca;
-          SF_ROW(h, fma(w3, da[j], w2));
-          SF_ROW(h, fma(h[j], da[j], w1));
-          SF_ROW(h, fma(h[j], da[j], w0c));
-        } else {
-        SF_ROW(y, da[j] * da[j]);
-        SF_ROW(h, fma(y[j], 1.0 / 24.0, -0.5));
-        SF_ROW(r, fma(y[j], 1.0 / 120.0, -1.0 / 6.0));
-        SF_ROW(h, fma(y[j], h[j], 1.0)); // cos da
-        SF_ROW(r, fma(y[j], r[j], 1.0));
-        SF_ROW(r, da[j] * r[j]); // sin da
-        SF_ROW(r, sa * r[j]);
-        SF_ROW(h, fma(ca, h[j], -r[j]));
-        SF_ROW(h, fma(0.5, h[j], 0.5));
-        }
+        // the window W(a) = 1/2 + cos(a)/2 at a_c + da as a cubic in da about a_c: derivatives -sin/2, -cos/2, +sin/2;
+        // |da| <= pi 1e-3 (the free point; 1e-5 for the six offset points): remainder da^4 / 48 <= 2e-12 (1e-21) --
+        // 3 rows instead of the 9 of cos / sin series of da and the addition theorem
+        const double w1 = -0.5 * sa, w2 = -0.25 * ca, w3 = (1.0 / 12.0) * sa, w0c = 0.5 + 0.5 * ca;
+        SF_ROW(h, fma(w3, da[j], w2));
+        SF_ROW(h, fma(h[j], da[j], w1));
+        SF_ROW(h, fma(h[j], da[j], w0c));
 #undef SF_ROW
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
@@ -1041,28 +977,10 @@ struct ScatteredModel {
           c8[7] += 1;
         }
       }
-      if constexpr (FUSED) {
-        if (k < side2.cap) {
-          side2.cs[k] = d2_t{ca, sa};
-          side2.rc[k] = rc;
-        } else { // a list longer than the side arrays: through the staging buffer
-          *chunk(rec, 4, k) = d2_t{rc, 0.0};
-          *chunk(rec, 5, k) = d2_t{ca, sa};
-        }
-        continue;
-      }
       *chunk(rec, 0, k) = qa;
       *chunk(rec, 1, k) = qb;
       *chunk(rec, 2, k) = qc;
       *chunk(rec, 3, k) = d2_t{qd.x, 0.0};
-#ifdef SRT_PROBE_EXTRA_STORES // (timing probe: the same 64 bytes once more, into chunks the weights overwrite later)
-      *chunk(rec, 6, k) = qa;
-      *chunk(rec, 7, k) = qb;
-      if (k < side.cap) {
-        *chunk(rec, 4, k) = qc;
-        *chunk(rec, 5, k) = qd;
-      }
-#endif
       if (k < side.cap) { // what the weights need waits in LDS ..
         side.a[k] = qa;
         side.b[k] = d2_t{q2, rc};
@@ -1100,7 +1018,7 @@ struct ScatteredModel {
     }
     // (block == one wave) the sums and the side arrays written above are read by other lanes next: LDS only -- unless the list is
     // longer than the side arrays, whose rest the weights pass reads back from the records (global memory: the stores must have landed)
-    if (n_list > (FUSED ? side2.cap : side.cap)) __syncthreads();
+    if (n_list > side.cap) __syncthreads();
     else wave_lds_sync();
     SRT_PHASE(2);
   }
@@ -1145,7 +1063,7 @@ struct ScatteredModel {
     const double o7[3] = {pg[7][0] - pg[0][0], pg[7][1] - pg[0][1], pg[7][2] - pg[0][2]};
     const double o7sq = o7[0] * o7[0] + o7[1] * o7[1] + o7[2] * o7[2];
     const Side side = side_of(list, n_list);
-    // ---- second-order tier (round 4, SRT_SCAT_TAYLOR).  The weight of a sample at a point is expanded about the centre in
+    // ---- second-order tier (round 4).  The weight of a sample at a point is expanded about the centre in
     // dr = r_g - r_c and dh = h_g - h_c:  w + dr (w_r + w_rh dh + (w_rr / 2) dr) + w_h dh, with (E = exp(-u), u = x**1.1, W the window)
     //   w = E W / 2,  w_r = E (L W + W') / 2,  w_rr = E ((L' + L^2) W + 2 L W' + W'') / 2,  L = -1.1 u / r,  L' = -0.11 u / r^2,
     //   w_h = w 1.1 u / h,  w_rh = w_r 1.1 u / h + w 1.21 u / (h r).
@@ -1159,33 +1077,30 @@ struct ScatteredModel {
     // to 4e-13, its central-difference gradient to 3e-8 median against the exact weights.  11 rows per point instead of 34;
     // every other stencil takes the series below, as in round 3.
     bool tay_all = false;
-    double tc1 = 0.0, tc2 = 0.0, ihc = 0.0;
-    double dh8[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if constexpr (SRT_SCAT_TAYLOR != 0) {
-      const double rmin = uni(o->rmin);
-      if (base_ok && rmin > 0.0) {
-        const double irm = fdiv(1.0, rmin + reps), iR = M.inv_radius;
-        const double umax = M.u11 * sh; // 1.1 u at the radius (u11: the model's constant 1.1 (radius + reps)**1.1 -- a log + exp chain per stencil before)
-        tay_all = dmax6 * irm <= 1.0e-3 && umax * (dmax6 * iR) <= 2.0e-4 && umax * etamax6 <= 2.0e-4 &&
-                  (!fit8[7] || (p7near && d7 * irm <= 1.0e-3 && umax * (d7 * iR) <= 2.0e-4 && umax * eta7 <= 2.0e-4));
-#ifdef SRT_PHASE_TIMING
-        if (lane == 0) {
-          const bool f7 = fit8[7] && !(p7near && d7 * irm <= 1.0e-3 && umax * (d7 * iR) <= 2.0e-4 && umax * eta7 <= 2.0e-4);
-          atomicAdd(&srt_tier_stats[tay_all ? 1 : (!(dmax6 * irm <= 1.0e-3) ? 3 : (!(umax * (dmax6 * iR) <= 2.0e-4) ? 4 : (!(umax * etamax6 <= 2.0e-4) ? 5 : (f7 ? 6 : 7))))], 1ull);
-        }
-#endif
-      }
+    const double rmin = uni(o->rmin);
+    if (base_ok && rmin > 0.0) {
+      const double irm = fdiv(1.0, rmin + reps), iR = M.inv_radius;
+      const double umax = M.u11 * sh; // 1.1 u at the radius (u11: the model's constant 1.1 (radius + reps)**1.1 -- a log + exp chain per stencil before)
+      tay_all = dmax6 * irm <= 1.0e-3 && umax * (dmax6 * iR) <= 2.0e-4 && umax * etamax6 <= 2.0e-4 &&
+                (!fit8[7] || (p7near && d7 * irm <= 1.0e-3 && umax * (d7 * iR) <= 2.0e-4 && umax * eta7 <= 2.0e-4));
 #ifdef SRT_PHASE_TIMING
       if (lane == 0) {
-        atomicAdd(&srt_tier_stats[0], 1ull);
-        if (!(base_ok && rmin > 0.0)) atomicAdd(&srt_tier_stats[2], 1ull);
+        const bool f7 = fit8[7] && !(p7near && d7 * irm <= 1.0e-3 && umax * (d7 * iR) <= 2.0e-4 && umax * eta7 <= 2.0e-4);
+        atomicAdd(&srt_tier_stats[tay_all ? 1 : (!(dmax6 * irm <= 1.0e-3) ? 3 : (!(umax * (dmax6 * iR) <= 2.0e-4) ? 4 : (!(umax * etamax6 <= 2.0e-4) ? 5 : (f7 ? 6 : 7))))], 1ull);
       }
 #endif
-      tc1 = -0.5 * pi_R, tc2 = -0.5 * pi_R * pi_R;
-      ihc = tay_all ? fdiv(1.0, hin8[0]) : 0.0;
-#pragma unroll
-      for (int gg = 0; gg < 8; ++gg) dh8[gg] = hin8[gg] - hin8[0];
     }
+#ifdef SRT_PHASE_TIMING
+    if (lane == 0) {
+      atomicAdd(&srt_tier_stats[0], 1ull);
+      if (!(base_ok && rmin > 0.0)) atomicAdd(&srt_tier_stats[2], 1ull);
+    }
+#endif
+    const double tc1 = -0.5 * pi_R, tc2 = -0.5 * pi_R * pi_R;
+    const double ihc = tay_all ? fdiv(1.0, hin8[0]) : 0.0;
+    double dh8[8];
+#pragma unroll
+    for (int gg = 0; gg < 8; ++gg) dh8[gg] = hin8[gg] - hin8[0];
     auto weigh_taylor = [&](int k, const d2_t s0, const d2_t s1, const d2_t s2) {
       const double q0 = s0.x, q1 = s0.y, q2 = s1.x, rc = s1.y, ca = s2.x, sa = s2.y;
       const double dc[3] = {q0 - pg[0][0], q1 - pg[0][1], q2 - pg[0][2]};
@@ -1365,7 +1280,6 @@ struct ScatteredModel {
     if (tay_all) { // (wave-uniform)
 #pragma unroll 1
       for (int k = lane; k < nlds; k += 64) weigh_taylor(k, side.a[k], side.b[k], side.c[k]);
-#if SRT_SCAT_REC_AHEAD
       // (a list longer than the side arrays -- most are: 423 samples on average against 306 slots: the rest comes back from the staging
       // records, one trip AHEAD, so that a trip's loads are not what its first instruction waits for)
       {
@@ -1381,13 +1295,6 @@ struct ScatteredModel {
           weigh_taylor(k, c0, d2_t{c1.x, c4.x}, c5);
         }
       }
-#else
-#pragma unroll 1
-      for (int k = nlds + lane; k < n_list; k += 64) {
-        const d2_t c0 = *chunk(rec, 0, k), c1 = *chunk(rec, 1, k), c4 = *chunk(rec, 4, k), c5 = *chunk(rec, 5, k);
-        weigh_taylor(k, c0, d2_t{c1.x, c4.x}, c5);
-      }
-#endif
     } else {
 #pragma unroll 1
     for (int k = lane; k < nlds; k += 64) weigh(k, side.a[k], side.b[k], side.c[k]);
@@ -1605,371 +1512,13 @@ struct ScatteredModel {
     return fi;
   }
 
-  // ---- the fused form of sf_weights + sf_sums (SRT_SCAT_FUSED) -------------------------------------------------------------
-  // One pass over the list, 64 samples (a tile) at a time:
-  //   weigh   lane = sample: the sample is gathered again from the sample array (one trip ahead of its use), {r_c, cos, sin}
-  //           come from pass 1 (LDS side arrays; staging buffer for a long list), the eight half-weights as in sf_weights (the same
-  //           series, row by row, the same fallbacks) -- and the finished 128-byte record goes into the tile in LDS;
-  //   sum     lane = (point g, 1 of 8): the group folds the tile's records into its normal equations, as sf_sums does from its ring.
-  // Records behind the list's end carry zero weights (and the last sample's coordinates: finite), so the sums test no index; the
-  // samples a point keeps above the weight mask are counted where the weights are made (one compare per point and sample, the
-  // count itself scalar).  The running sums stay in registers across the weighing code: at two waves per SIMD that is 150 of the
-  // 256, so the series run over the points in two halves there (SRT_SCAT_CHAIN_SPLIT).
-#ifndef SRT_SCAT_CHAIN_SPLIT
-#define SRT_SCAT_CHAIN_SPLIT (SRT_SCAT_WAVES == 2)
-#endif
-  template <int J>
-  __device__ __noinline__ Fit4 sf_fused(const double (&p_in)[3], bool live, unsigned long long livemask, int npts, int n_list,
-                                        SRT_LDS const int *list, double *rec_flat, double dmax6, double d7, bool p7near,
-                                        int &kept_out) const {
-    const ScatteredModel M = uniform_copy();
-    Fit4 fi;
-    const double p[3] = {p_in[0], p_in[1], p_in[2]};
-    const double radius = M.radius;
-    SRT_AS1 double *const rec = (SRT_AS1 double *)rec_flat;
-    const int lane = threadIdx.x, g = lane >> 3, sub = lane & 7;
-    const double r2 = radius * radius, pi_R = PI / radius, reps = radius * 5.0e-16;
-    constexpr bool usemask = true;
-    SRT_PHASE_BEGIN(list);
-    SRT_LDS const Pass1Out *o = pass1_out(list);
-    double hin8[8], pg[8][3];
-    bool fit8[8], lv8[8];
-    int kept_c[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // wave-uniform
-#pragma unroll
-    for (int gg = 0; gg < 8; ++gg) {
-      hin8[gg] = uni(o->hin8[gg]);
-      lv8[gg] = (livemask >> (8 * gg)) & 1ull;
-      fit8[gg] = lv8[gg] && gg < npts && uni(o->cnt8[gg]) >= J;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) pg[gg][k] = from_lane(p[k], 8 * gg);
-    }
-    const bool fit = live && o->cnt8[g] >= J;
-    double eta8[8], etamax6 = 0.0;
-#pragma unroll
-    for (int gg = 0; gg < 8; ++gg) {
-      eta8[gg] = fdiv(hin8[0] - hin8[gg], hin8[gg]);
-      if (gg < 7 && fit8[gg]) etamax6 = fmax(etamax6, fabs(eta8[gg]));
-    }
-    const double eta7 = fit8[7] ? fabs(eta8[7]) : 0.0;
-    const bool base_ok = M.exact != 1 && uni(o->cnt8[0]) >= 1 && hin8[0] > 0.0 && etamax6 <= 1.0e-3;
-    const double sh = base_ok ? fm::exp_any(-1.1 * fm::log_pos(hin8[0] * 0.25)) : 0.0; // (h_c / 4)**-1.1: u_c = a sh
-    const double da3[3] = {pg[1][0] - pg[0][0], pg[3][1] - pg[0][1], pg[5][2] - pg[0][2]};
-    const double mda3[3] = {pg[2][0] - pg[0][0], pg[4][1] - pg[0][1], pg[6][2] - pg[0][2]};
-    const double o7[3] = {pg[7][0] - pg[0][0], pg[7][1] - pg[0][1], pg[7][2] - pg[0][2]};
-    const double o7sq = o7[0] * o7[0] + o7[1] * o7[1] + o7[2] * o7[2];
-    const double pc[3] = {pg[0][0], pg[0][1], pg[0][2]};
-    const Side2 side = side2_of(list, n_list);
-    // ---- the running sums (as sf_sums)
-    constexpr int NT = J * (J + 1) / 2;
-    constexpr bool O3 = J == 20;
-    double A[(O3 || J == 10) ? 1 : NT], b[O3 ? 1 : J][4];
-    double Mm[J == 10 ? Moments::N : 1];
-    typename std::conditional<O3, Sums20, int>::type S20;
-    if constexpr (O3) S20.zero();
-#pragma unroll
-    for (int t = 0; t < ((O3 || J == 10) ? 1 : NT); ++t) A[t] = 0.0;
-#pragma unroll
-    for (int t = 0; t < (J == 10 ? Moments::N : 1); ++t) Mm[t] = 0.0;
-#pragma unroll
-    for (int a = 0; a < (O3 ? 1 : J); ++a)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) b[a][s] = 0.0;
-    auto fold = [&](double w2, double d0, double d1, double d2, const double (&ln)[4]) {
-      if constexpr (O3) {
-        S20.fold(w2, d0, d1, d2, ln);
-      } else if constexpr (J == 10) {
-        const double dd[3] = {d0, d1, d2};
-        double wm[Moments::LOW], m[10];
-        wm[0] = w2;
-        Moments::monomials_from(wm, dd, std::make_integer_sequence<int, Moments::LOW - 1>{});
-#pragma unroll
-        for (int i = 0; i < Moments::LOW; ++i) Mm[i] += wm[i];
-        Moments::fold_leaves(Mm, wm, dd, std::make_integer_sequence<int, Moments::N - Moments::LOW>{});
-        Moments::firsts(wm, m, std::make_integer_sequence<int, 10>{}); // w m_a
-#pragma unroll
-        for (int a = 0; a < 10; ++a)
-#pragma unroll
-          for (int s = 0; s < 4; ++s) b[a][s] += m[a] * ln[s];
-      } else {
-        double m[J];
-        monomials<J>(d0, d1, d2, m);
-        int t = 0;
-#pragma unroll
-        for (int a = 0; a < J; ++a) {
-          double wa = w2 * m[a];
-#pragma unroll
-          for (int cI = a; cI < J; ++cI) A[t++] += wa * m[cI];
-#pragma unroll
-          for (int s = 0; s < 4; ++s) b[a][s] += wa * ln[s];
-        }
-      }
-    };
-    // ---- the eight half-weights of one sample (sf_weights' arithmetic; w8[] out)
-    auto weigh = [&](const double q0, const double q1, const double q2, const double rc, const double ca, const double sa, double (&w8)[8]) {
-      const double dc[3] = {q0 - pc[0], q1 - pc[1], q2 - pc[2]};
-      const double ssc = dc[0] * dc[0] + dc[1] * dc[1] + dc[2] * dc[2];
-      const double xr = rc + reps;
-      const double a11 = xr * fm::exp_any(0.1 * fm::log_pos(xr));
-      const double inv = fdiv(1.0, xr), inv2 = inv * inv, hinv = 0.5 * inv;
-      const double u = a11 * sh;
-      const double E = fm::exp_any(-u);
-      double tb6 = dmax6 * inv, tb7 = d7 * inv;
-      tb6 = tb6 + etamax6 * (1.0 + tb6);
-      tb7 = tb7 + eta7 * (1.0 + tb7);
-      const bool dir6 = !(base_ok && tb6 <= 1.0e-3 && u * 1.2 * tb6 <= 1.0e-3);
-      const bool dir7 = dir6 || !(p7near && tb7 <= 1.0e-3 && u * 1.2 * tb7 <= 1.0e-3);
-      const double Eh = 0.5 * E, thr = 0.5 * 1.0e-16;
-      const double w0 = Eh * (0.5 + 0.5 * ca);
-      w8[0] = (fit8[0] && ssc < r2 && (w0 > thr || !usemask)) ? w0 : 0.0; // strictly inside (kdtree_mod.f95:171)
-      w8[7] = 0.0;
-      // chains FIRST .. FIRST + NQ - 1 (chain j = point j + 1), row by row with the order pinned (see sf_weights)
-      auto chains = [&](auto first, auto nq) {
-        constexpr int F0 = decltype(first)::value, NQ = decltype(nq)::value;
-#define SF_ROW(dst, expr)                                                                                              \
-  _Pragma("unroll") for (int j = 0; j < NQ; ++j) dst[j] = expr;                                                        \
-  _Pragma("unroll") for (int j = 0; j < NQ; ++j) asm volatile("" : "+v"(dst[j]))
-        double t[NQ], tin[NQ], pl[NQ], dr[NQ], au[NQ], X[NQ], cd[NQ], sd[NQ];
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-          const int jj = F0 + j;
-          if (jj < 6) {
-            const double dl = (jj & 1) ? mda3[jj >> 1] : da3[jj >> 1];
-            const double x = fma(-2.0, dc[jj >> 1], dl);
-            t[j] = dl * x;
-            tin[j] = fma(dl, x, ssc);
-          } else {
-            t[j] = o7sq - 2.0 * (o7[0] * dc[0] + o7[1] * dc[1] + o7[2] * dc[2]);
-            tin[j] = ssc + t[j];
-          }
-        }
-        SF_ROW(au, t[j] * inv2); // eps
-        SF_ROW(pl, fma(au[j], 0.0546875, -0.078125));
-        SF_ROW(pl, fma(au[j], pl[j], 0.125));
-        SF_ROW(pl, fma(au[j], pl[j], -0.25));
-        SF_ROW(pl, fma(au[j], pl[j], 1.0));
-        SF_ROW(dr, t[j] * hinv); // (= (0.5 t) inv to the bit)
-        SF_ROW(dr, dr[j] * pl[j]);
-        SF_ROW(au, dr[j] * inv); // tau
-        SF_ROW(au, fma(au[j], 1.0 + eta8[F0 + j + 1], eta8[F0 + j + 1]));
-        SF_ROW(pl, fma(au[j], 0.0078375, -0.0165));
-        SF_ROW(pl, fma(au[j], pl[j], 0.055));
-        SF_ROW(pl, fma(au[j], pl[j], 1.1));
-        SF_ROW(au, au[j] * pl[j]); // (1 + tau)**1.1 - 1
-        SF_ROW(au, u * au[j]);     // du
-        SF_ROW(pl, fma(au[j], -1.0 / 120.0, 1.0 / 24.0));
-        SF_ROW(pl, fma(au[j], pl[j], -1.0 / 6.0));
-        SF_ROW(pl, fma(au[j], pl[j], 0.5));
-        SF_ROW(pl, fma(au[j], pl[j], -1.0));
-        SF_ROW(X, fma(au[j], pl[j], 1.0)); // exp(-du)
-        SF_ROW(dr, dr[j] * pi_R);          // da
-        SF_ROW(au, dr[j] * dr[j]);
-        SF_ROW(cd, fma(au[j], 1.0 / 24.0, -0.5));
-        SF_ROW(sd, fma(au[j], 1.0 / 120.0, -1.0 / 6.0));
-        SF_ROW(cd, fma(au[j], cd[j], 1.0));
-        SF_ROW(sd, fma(au[j], sd[j], 1.0));
-        SF_ROW(sd, dr[j] * sd[j]);
-        SF_ROW(sd, sa * sd[j]);
-        SF_ROW(X, Eh * X[j]);
-        SF_ROW(cd, fma(ca, cd[j], -sd[j]));
-        SF_ROW(cd, fma(cd[j], 0.5, 0.5));
-        SF_ROW(X, X[j] * cd[j]);
-#undef SF_ROW
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) w8[F0 + j + 1] = (fit8[F0 + j + 1] && tin[j] < r2 && (X[j] > thr || !usemask)) ? X[j] : 0.0;
-      };
-      using I0 = std::integral_constant<int, 0>;
-      using I3 = std::integral_constant<int, 3>;
-      using I4 = std::integral_constant<int, 4>;
-      if constexpr (SRT_SCAT_CHAIN_SPLIT != 0) {
-        chains(I0{}, I3{});
-        if (fit8[7]) chains(I3{}, I4{}); // (wave-uniform)
-        else chains(I3{}, I3{});
-      } else {
-        if (fit8[7]) chains(I0{}, std::integral_constant<int, 7>{}); // (wave-uniform)
-        else chains(I0{}, std::integral_constant<int, 6>{});
-      }
-      if (dir6 || (dir7 && fit8[7])) { // rare, per lane: etainv() itself at the points that cannot take the series
-#pragma unroll 1
-        for (int gg = 0; gg < 8; ++gg) {
-          if (gg < 7 && !dir6) continue;
-          double px = pg[0][0], py = pg[0][1], pz = pg[0][2], hg = hin8[0];
-          bool fg = fit8[0];
-#pragma unroll
-          for (int t = 1; t < 8; ++t) {
-            px = gg == t ? pg[t][0] : px, py = gg == t ? pg[t][1] : py, pz = gg == t ? pg[t][2] : pz;
-            hg = gg == t ? hin8[t] : hg;
-            fg = gg == t ? fit8[t] : fg;
-          }
-          const double e0 = q0 - px, e1 = q1 - py, e2 = q2 - pz;
-          const double ss = e0 * e0 + e1 * e1 + e2 * e2;
-          double e = (fg && ss < r2) ? 0.5 * M.etainv_at(ss, hg) : 0.0;
-          e = (usemask && !(e > thr)) ? 0.0 : e; // :316-317
-#pragma unroll
-          for (int t = 0; t < 8; ++t) w8[t] = gg == t ? e : w8[t];
-        }
-      }
-    };
-    // ---- the pass
-    SRT_LDS char *const tile = tile_of(list);
-    const int nchunk = (n_list + 63) >> 6; // wave-uniform
-    const bool any = __any(fit);
-    // (one tile ahead: the next tile's gather is in flight while this one is weighed and summed)
-    d2_t na = {0.0, 0.0}, nb = na, nc = na, nd = na, n4 = na, n5 = na;
-    auto fetch = [&](int k) {
-      const int kc = k < n_list ? k : n_list - 1;
-      const SRT_AS1 d2_t *q = (const SRT_AS1 d2_t *)(M.gpts() + (size_t)list[kc] * 8);
-      na = q[0], nb = q[1], nc = q[2], nd = q[3];
-      if (kc >= side.cap) {
-        n4 = *chunk(rec, 4, kc);
-        n5 = *chunk(rec, 5, kc);
-      }
-    };
-    if (any && nchunk > 0) fetch(lane);
-    const int slot = (g == 7) ? 15 : 8 + g;
-    const unsigned tile0 = (unsigned)(unsigned long long)tile + (unsigned)(sub * 16);
-    const unsigned slot_off = (unsigned)((slot >> 1) * 1024 + (slot & 1) * 8);
-#pragma unroll 1
-    for (int c = 0; c < nchunk && any; ++c) {
-      const int k = c * 64 + lane;
-      const int kc = k < n_list ? k : n_list - 1;
-      const d2_t qa = na, qb = nb, qc = nc, qd = nd, q4 = n4, q5 = n5;
-      double rc, ca, sa;
-      if (kc < side.cap) {
-        const d2_t cs = side.cs[kc];
-        ca = cs.x, sa = cs.y;
-        rc = side.rc[kc];
-      } else {
-        rc = q4.x, ca = q5.x, sa = q5.y;
-      }
-      if (c + 1 < nchunk) fetch(k + 64);
-      double w8[8];
-      weigh(qa.x, qa.y, qb.x, rc, ca, sa, w8);
-      if (k >= n_list) { // behind the list's end: no weight at any point
-#pragma unroll
-        for (int t = 0; t < 8; ++t) w8[t] = 0.0;
-      }
-#pragma unroll
-      for (int gg = 0; gg < 8; ++gg) kept_c[gg] += __popcll(__ballot(w8[gg] != 0.0));
-      {
-        SRT_LDS d2_t *tl = (SRT_LDS d2_t *)tile + lane;
-        tl[0] = qa;
-        tl[64] = qb;
-        tl[128] = qc;
-        tl[192] = d2_t{qd.x, 0.0};
-        tl[256] = d2_t{w8[0], w8[1]};
-        tl[320] = d2_t{w8[2], w8[3]};
-        tl[384] = d2_t{w8[4], w8[5]};
-        tl[448] = d2_t{w8[6], w8[7]};
-      }
-      __syncthreads(); // block == one wave: the tile written above is read by other lanes below
-      if (fit) {
-        struct RecRegs {
-          d2_t c0, c1, c2;
-          double ln3, w2;
-        };
-        auto rd = [&](RecRegs &R, int i) {
-          const unsigned ra = tile0 + (unsigned)(i * 128);
-          asm volatile("ds_read_b128 %0, %5\n\t"
-                       "ds_read_b128 %1, %5 offset:1024\n\t"
-                       "ds_read_b128 %2, %5 offset:2048\n\t"
-                       "ds_read_b64 %3, %5 offset:3072\n\t"
-                       "ds_read_b64 %4, %6"
-                       : "=&v"(R.c0), "=&v"(R.c1), "=&v"(R.c2), "=&v"(R.ln3), "=&v"(R.w2)
-                       : "v"(ra), "v"(ra + slot_off)
-                       : "memory");
-        };
-        auto landed = [&](RecRegs &R) {
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(R.c0), "+v"(R.c1), "+v"(R.c2), "+v"(R.ln3), "+v"(R.w2) : : "memory");
-        };
-        auto use = [&](const RecRegs &R) {
-          const double ln[4] = {R.c1.y, R.c2.x, R.c2.y, R.ln3};
-          fold(R.w2, R.c0.x - p[0], R.c0.y - p[1], R.c1.x - p[2], ln);
-        };
-        RecRegs Ra, Rb;
-        rd(Ra, 0);
-        landed(Ra);
-#pragma unroll 1
-        for (int i = 0; i < 8; i += 2) {
-          rd(Rb, i + 1);
-          use(Ra);
-          landed(Rb);
-          rd(Ra, i + 2 < 8 ? i + 2 : 7); // (the last one is read for nothing)
-          use(Rb);
-          landed(Ra);
-        }
-      }
-      __syncthreads(); // (the tile is rewritten next trip)
-    }
-    {
-      int kk = kept_c[0];
-#pragma unroll
-      for (int t = 1; t < 8; ++t) kk = g == t ? kept_c[t] : kk;
-      kept_out = kk;
-    }
-    SRT_PHASE(4);
-    // combine the 8 lanes' partial sums and solve (as sf_sums)
-    fi.v[0] = fi.v[1] = fi.v[2] = fi.v[3] = 0.0;
-    if (any) {
-      if constexpr (O3) {
-        S20.reduce([](double v) { return group_sum(v); });
-        if (fit) {
-          double f4[4];
-          if (S20.solve(f4) == 0) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) fi.v[s] = f4[s];
-          }
-        }
-      } else if constexpr (J == 10) {
-        SRT_LDS double *area = (SRT_LDS double *)const_cast<SRT_LDS int *>(list) + 80 * g; // (the list and the side arrays are dead by now)
-        static_assert(Moments::N == 35, "area layout: 35 moments, then 10 x 4 right-hand sums");
-        auto sumof = [&](auto ic) -> double {
-          constexpr int t = decltype(ic)::value;
-          if constexpr (t < 35) return Mm[t];
-          else if constexpr (t < 75) return b[(t - 35) >> 2][(t - 35) & 3];
-          else return 0.0;
-        };
-        auto pairs = [&](auto self, auto ic) -> void {
-          constexpr int t = decltype(ic)::value;
-          if constexpr (t < 75) {
-            const double v = group_sum2(sumof(std::integral_constant<int, t>{}), sumof(std::integral_constant<int, t + 1>{}));
-            if ((sub & 3) == ((t >> 1) & 3) && t + (sub >> 2) < 75) area[t + (sub >> 2)] = v;
-            self(self, std::integral_constant<int, t + 2>{});
-          }
-        };
-        pairs(pairs, std::integral_constant<int, 0>{});
-        __syncthreads(); // block == one wave: the totals written above are read by the group's other lanes below
-        if (fit) {
-          double f1;
-          if (solve10_parked(area, sub & 3, f1) == 0) fi.v[0] = fi.v[1] = fi.v[2] = fi.v[3] = f1; // (this lane's species only)
-        }
-        __syncthreads(); // (the area is list space again)
-      } else {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) A[t] = group_sum(A[t]);
-#pragma unroll
-        for (int a = 0; a < J; ++a)
-#pragma unroll
-          for (int s = 0; s < 4; ++s) b[a][s] = group_sum(b[a][s]);
-        if (fit) {
-          double f4[4];
-          if (solve_fit<J>(A, b, f4) == 0) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) fi.v[s] = f4[s];
-          }
-        }
-      }
-    }
-    SRT_PHASE(5);
-    return fi;
-  }
-
   // pass 1 + weights in one out-of-line body (one call, one set of registers saved around it); returns whether this group's
   // fit exists: its point has at least J samples (else status 2: too few samples, lsinterp_mod.f95:262-264)
   template <int J>
   __device__ __noinline__ bool sf_prepare(const double (&p)[3], bool live, unsigned long long livemask, int npts, int n_list,
                                           SRT_LDS const int *list, double *rec, double dmax6, double d7, bool p7near) const {
     sf_pass1(p, livemask, npts, n_list, list, rec, dmax6, d7, p7near);
-    if constexpr (!FUSED) sf_weights<J>(p, live, livemask, npts, n_list, list, rec, dmax6, d7, p7near, true);
+    sf_weights<J>(p, live, livemask, npts, n_list, list, rec, dmax6, d7, p7near, true);
     return live && pass1_out(list)->cnt8[threadIdx.x >> 3] >= J;
   }
   // `redo`: some point threw out too many samples (fewer than J kept: "use them all", lsinterp_mod.f95:319-323).  The list, the
@@ -1979,19 +1528,9 @@ struct ScatteredModel {
   __device__ __forceinline__ Fit4 shared_fit(const double (&p)[3], bool live, unsigned long long livemask, int npts, int n_list,
                                              SRT_LDS const int *list, double *rec, double dmax6, double d7, bool p7near,
                                              bool &redo) const {
-    if constexpr (FUSED) {
-      if (n_list > FUSED_LIST_CAP) { // (wave-uniform) the list leaves the tile no room: the own-list path serves this stencil
-        redo = true;
-        Fit4 none;
-        none.v[0] = none.v[1] = none.v[2] = none.v[3] = 0.0;
-        return none;
-      }
-    }
     const bool fit = sf_prepare<J>(p, live, livemask, npts, n_list, list, rec, dmax6, d7, p7near);
     int kept = 0;
-    Fit4 fi;
-    if constexpr (FUSED) fi = sf_fused<J>(p, live, livemask, npts, n_list, list, rec, dmax6, d7, p7near, kept);
-    else fi = sf_sums<J>(p, fit, n_list, list, rec, kept);
+    const Fit4 fi = sf_sums<J>(p, fit, n_list, list, rec, kept);
     redo = __any(fit && kept < J);
     return fi;
   }

@@ -1,4 +1,4 @@
-"""modelnum 4: the second-order weight tier of the shared stencil path (srt_scattered.hpp sf_weights, SRT_SCAT_TAYLOR) at
+"""modelnum 4: the second-order weight tier of the shared stencil path (srt_scattered.hpp sf_weights, second-order tier) at
 its design accuracy, and the stencils it must decline.
 
 The tier expands every sample's weight at the six offset points about the stencil centre.  It is chosen once per stencil when
