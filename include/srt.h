@@ -171,6 +171,33 @@ int srt_build_grid(srt_model *src, int compder, int nx, int ny, int nz, const do
                    double *derivs);
 int srt_model_create_interp_from_model(srt_model *src, int compder, int nx, int ny, int nz,
                                        const double bounds[6], int yearday, int msec, srt_model **out);
+/* modelnum=3 has two device layouts of the same model (same lookups, same answers):
+ *   SRT_INTERP_EXPANDED: coef[cell][species][64], the 64 tricubic coefficients of every cell expanded once at creation; a
+ *     lookup is one contiguous read.  (nx+1)(ny+1)(nz+1) nspec 512 bytes.  What the three creators above make.
+ *   SRT_INTERP_NODES: nodes[k][j][i][species][8], the eight values per node the coefficients are formed from, which a
+ *     lookup does itself.  nx ny nz nspec 64 bytes: an eighth, for grids (or sets of grids) the expanded table has no room
+ *     for; more arithmetic per lookup.
+ *   SRT_INTERP_AUTO: EXPANDED when creation fits into the device's free memory, else NODES, else SRT_ENOMEM
+ *     (srt_interp_layout_choose applied to hipMemGetInfo's free bytes).
+ * The _layout creators take the arguments of their namesakes plus the layout; any other layout number is SRT_EINVAL.
+ * srt_model_interp_layout: the layout a handle has (0 or 1), -1 for other kinds; srt_model_kind answers 3 for both. */
+#define SRT_INTERP_EXPANDED 0
+#define SRT_INTERP_NODES 1
+#define SRT_INTERP_AUTO 2
+int srt_model_create_interp_layout(int nspec, int nx, int ny, int nz, const double bounds[6],
+                                   const double *qs, const double *ms, const double *F,
+                                   const double *const *derivs, int yearday, int msec, int layout, srt_model **out);
+int srt_model_create_interp_file_layout(const char *gridfile, int yearday, int msec, int layout, srt_model **out);
+int srt_model_create_interp_from_model_layout(srt_model *src, int compder, int nx, int ny, int nz,
+                                              const double bounds[6], int yearday, int msec, int layout, srt_model **out);
+int srt_model_interp_layout(const srt_model *m);
+/* Pure host code, needs no GPU.  layout = SRT_INTERP_EXPANDED or SRT_INTERP_NODES.
+ *   srt_interp_layout_bytes: *table = bytes of the table, *peak = the most that creation holds at once (the eight grid
+ *     arrays and the table); either may be NULL.
+ *   srt_interp_layout_choose: SRT_INTERP_EXPANDED if its peak fits into free_bytes, else SRT_INTERP_NODES if that fits,
+ *     else SRT_ENOMEM. */
+int srt_interp_layout_bytes(int nspec, int nx, int ny, int nz, int layout, int64_t *table, int64_t *peak);
+int srt_interp_layout_choose(int nspec, int nx, int ny, int nz, int64_t free_bytes);
 /* The other builder of the step before the path: the random / adaptive sample set of
  * gcpm_dens_model_buildgrid_random.f95:228-407 + randomsampling_mod.f95:27-200 (recursivesampler), with any model
  * handle in place of GCPM, generated and refined ON THE DEVICE.  Stage order and per-stage rules are the reference's:
@@ -210,6 +237,9 @@ int srt_model_kind(const srt_model *m);  /* 1, 3, 4, 5, 6 or 7 */
 int srt_model_nspec(const srt_model *m);
 int srt_model_species(const srt_model *m, double qs[SRT_MAXSPEC], double ms[SRT_MAXSPEC]);
 int64_t srt_model_device_bytes(const srt_model *m);
+/* device address of the handle's model struct, as the kernels read it (its type belongs to the handle's kind and layout: csrc/);
+ * for probes of device-only code that run beside the library in the same process.  Valid until srt_model_destroy. */
+const void *srt_model_device_struct(const srt_model *m);
 
 /* ---- layered entry points (each mirrors one reference procedure, batched over n items) ---- */
 /* funcPlasmaParams: x[n][3] -> qs,Ns,ms,nus [n][4], B0[n][3] */

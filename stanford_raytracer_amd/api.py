@@ -77,6 +77,14 @@ def lib():
     L.srt_model_create_interp_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp)]
     L.srt_model_create_interp.argtypes = [C.c_int] * 4 + [dp, dp, dp, dp, C.POINTER(dp), C.c_int, C.c_int,
                                                           C.POINTER(vp)]
+    L.srt_model_create_interp_file_layout.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.srt_model_create_interp_layout.argtypes = [C.c_int] * 4 + [dp, dp, dp, dp, C.POINTER(dp), C.c_int, C.c_int, C.c_int,
+                                                                 C.POINTER(vp)]
+    L.srt_model_create_interp_from_model_layout.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int,
+                                                            C.c_int, C.POINTER(vp)]
+    L.srt_model_interp_layout.argtypes = [vp]
+    L.srt_interp_layout_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.srt_interp_layout_choose.argtypes = [C.c_int] * 4 + [C.c_int64]
     L.srt_model_create_scattered_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
                                                   C.c_double, C.POINTER(vp)]
     L.srt_model_create_scattered_file_root.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
@@ -94,6 +102,8 @@ def lib():
     L.srt_model_nspec.argtypes = [vp]
     L.srt_model_species.argtypes = [vp, dp, dp]
     L.srt_model_device_bytes.argtypes = [vp]
+    L.srt_model_device_struct.argtypes = [vp]
+    L.srt_model_device_struct.restype = vp
     L.srt_model_device_bytes.restype = C.c_int64
     L.srt_plasma_params.argtypes = [vp, C.c_int64, dp, dp, dp, dp, dp, dp]
     L.srt_dispersion.argtypes = [vp, C.c_int64, dp, dp, dp, dp]
@@ -141,6 +151,36 @@ def lib():
 SRT_OK, SRT_EINVAL, SRT_EIO, SRT_EDEVICE, SRT_ENOMEM = 0, -1, -2, -3, -4
 
 
+# device layouts of the interp model (include/srt.h)
+INTERP_EXPANDED, INTERP_NODES, INTERP_AUTO = 0, 1, 2
+INTERP_LAYOUTS = {"expanded": INTERP_EXPANDED, "nodes": INTERP_NODES, "auto": INTERP_AUTO}
+
+
+def _layout(layout):
+    """'expanded' | 'nodes' | 'auto' (or the number) -> SRT_INTERP_*"""
+    if isinstance(layout, str):
+        if layout not in INTERP_LAYOUTS:
+            raise ValueError("layout %r is not one of %s" % (layout, ", ".join(INTERP_LAYOUTS)))
+        return INTERP_LAYOUTS[layout]
+    return int(layout)
+
+
+def interp_layout_bytes(nspec, nx, ny, nz, layout):
+    """-> (bytes of the table, the most that creation holds on the device at once); needs no GPU."""
+    t, pk = C.c_int64(), C.c_int64()
+    _check(lib().srt_interp_layout_bytes(nspec, nx, ny, nz, _layout(layout), C.byref(t), C.byref(pk)))
+    return t.value, pk.value
+
+
+def interp_layout_choose(nspec, nx, ny, nz, free_bytes):
+    """What layout='auto' picks with `free_bytes` free on the device: INTERP_EXPANDED or INTERP_NODES; SrtError (SRT_ENOMEM)
+    when neither fits.  Needs no GPU."""
+    rc = lib().srt_interp_layout_choose(nspec, nx, ny, nz, int(free_bytes))
+    if rc < 0:
+        _check(rc)
+    return rc
+
+
 def _check(rc):
     if rc != 0:
         raise SrtError("srt error %d: %s" % (rc, (lib().srt_last_error() or b"").decode()))
@@ -184,14 +224,15 @@ class Model:
         return cls(h)
 
     @classmethod
-    def interp_file(cls, gridfile, yearday=2010001, msec=0):
+    def interp_file(cls, gridfile, yearday=2010001, msec=0, layout="expanded"):
+        """layout: 'expanded' (the coefficient table), 'nodes' (the node table, an eighth of the bytes) or 'auto'."""
         h = C.c_void_p()
-        _check(lib().srt_model_create_interp_file(os.fsencode(gridfile), yearday, msec, C.byref(h)))
+        _check(lib().srt_model_create_interp_file_layout(os.fsencode(gridfile), yearday, msec, _layout(layout), C.byref(h)))
         return cls(h)
 
     @classmethod
-    def interp(cls, F, bounds, qs, ms, derivs=None, yearday=2010001, msec=0):
-        """F[nz, ny, nx, nspec] = ln N_s in the grid file's order (species fastest, then x, y, z)."""
+    def interp(cls, F, bounds, qs, ms, derivs=None, yearday=2010001, msec=0, layout="expanded"):
+        """F[nz, ny, nx, nspec] = ln N_s in the grid file's order (species fastest, then x, y, z).  layout: as interp_file."""
         F = _f64(F)
         nz, ny, nx, ns = F.shape
         b, q, m = _f64(bounds, 6), _f64(qs, ns), _f64(ms, ns)
@@ -201,8 +242,8 @@ class Model:
             keep = [_f64(d, F.shape) for d in derivs]
             dptr = (dp * 7)(*[_dp(d) for d in keep])
         h = C.c_void_p()
-        _check(lib().srt_model_create_interp(ns, nx, ny, nz, _dp(b), _dp(q), _dp(m), _dp(F), dptr, yearday, msec,
-                                             C.byref(h)))
+        _check(lib().srt_model_create_interp_layout(ns, nx, ny, nz, _dp(b), _dp(q), _dp(m), _dp(F), dptr, yearday, msec,
+                                                    _layout(layout), C.byref(h)))
         return cls(h)
 
     @classmethod
@@ -296,12 +337,18 @@ class Model:
             lib().srt_free(out)
         return res, list(counts)
 
-    def to_interp(self, nx, ny, nz, bounds, compder=False, yearday=2010001, msec=0):
-        """A modelnum=3 model tabulating this one, built without leaving the device."""
+    def to_interp(self, nx, ny, nz, bounds, compder=False, yearday=2010001, msec=0, layout="expanded"):
+        """A modelnum=3 model tabulating this one, built without leaving the device.  layout: as interp_file."""
         h = C.c_void_p()
-        _check(lib().srt_model_create_interp_from_model(self.h, int(bool(compder)), nx, ny, nz,
-                                                        _dp(_f64(bounds, (6,))), yearday, msec, C.byref(h)))
+        _check(lib().srt_model_create_interp_from_model_layout(self.h, int(bool(compder)), nx, ny, nz,
+                                                               _dp(_f64(bounds, (6,))), yearday, msec, _layout(layout),
+                                                               C.byref(h)))
         return Model(h)
+
+    @property
+    def layout(self):
+        """Device layout of an interp model: INTERP_EXPANDED (0) or INTERP_NODES (1); -1 for the other kinds."""
+        return lib().srt_model_interp_layout(self.h)
 
     def set_field(self, use_igrf=0, use_tsyganenko=0, igrf_coeff_file=None, parmod=None):
         """--use_igrf / --use_tsyganenko of the driver; parmod = Pdyn, Dst, ByIMF, BzIMF, W1..W6 (--tsyganenko_*)."""

@@ -66,13 +66,14 @@ def build(force=False, verbose=False):
 
 PROBE = os.path.join(LIBDIR, "libsrt_fastmath_probe.so")
 PROBE_DIR = os.path.join(PKG, "..", "tests", "native")
-PROBE_SRCS = ["fastmath_probe.hip", "igrf_probe.hip"]
+PROBE_SRCS = ["fastmath_probe.hip", "igrf_probe.hip", "interp_nodes_probe.hip"]
 PROBE_HDRS = ["fastmath_ops.hpp"]
 
 
 def build_probe(force=False, verbose=False):
     """The test probes of device-only code: the elementary functions (tests/native/fastmath_probe.hip, for
-    tests/test_gpu_fastmath.py) and the IGRF synthesis (tests/native/igrf_probe.hip, for tests/test_igrf_edges.py).  A library
+    tests/test_gpu_fastmath.py), the IGRF synthesis (tests/native/igrf_probe.hip, for tests/test_igrf_edges.py) and the interp
+    model's stencil lookup in both layouts (tests/native/interp_nodes_probe.hip, for tests/test_gpu_interp_nodes.py).  A library
     of its own with the library's flags.  libsrt_hip.so is not linked against it."""
     srcs = [os.path.abspath(os.path.join(PROBE_DIR, f)) for f in PROBE_SRCS]
     srcs = [s for s in srcs if os.path.exists(s)]  # each probe stands alone: a tree without one of them still builds the others

@@ -23,12 +23,12 @@
 #include "srt_kernels.hpp"
 #include "srt_ngo_setup.hpp"
 #include "srt_scattered.hpp"
+#include "srt_interp_nodes.hpp"
 #include "srt_simple3d.hpp"
 #include "srt_at64thch.hpp"
 #include "srt_sampler.hpp"
 #include "srt_damping.hpp"
 #include <hipcub/hipcub.hpp>
-#include "tricubic_matrix.h"
 
 using namespace srt;
 
@@ -181,7 +181,8 @@ extern "C" int srt_device_info(char *name, int name_len, int *cu_count, int64_t 
 }
 
 // ------------------------------------------------------------------------------------------ model
-enum ModelKind { KIND_NGO = 1, KIND_INTERP = 3, KIND_SCATTERED = 4, KIND_NGO3D = 5, KIND_SIMPLE3D = 6, KIND_AT64THCH = 7 }; // the driver's modelnum
+enum ModelKind { KIND_NGO = 1, KIND_INTERP = 3, KIND_SCATTERED = 4, KIND_NGO3D = 5, KIND_SIMPLE3D = 6, KIND_AT64THCH = 7, // the driver's modelnum
+                 KIND_INTERP_NODES = 30 }; // internal: modelnum 3 in its node-table layout (srt_model_kind answers 3)
 
 struct srt_model {
   int kind = 0, nspec = 0;
@@ -191,12 +192,13 @@ struct srt_model {
   // set, and geopack's own PSI for the table's date (srt_host::igrf_setup)
   bool have_table = false, have_parmod = false;
   float geopack_psi = 0.f;
-  std::tuple<NgoModel, InterpModel, ScatteredModel, Ngo3dModel, Simple3dModel, At64ThChModel> host{}; // the host copy of `kind`'s struct
+  std::tuple<NgoModel, InterpModel, ScatteredModel, Ngo3dModel, Simple3dModel, At64ThChModel, InterpNodesModel> host{}; // the host copy of `kind`'s struct
   template <class M> M &as() { return std::get<M>(host); }
   DevBuf<double> d_pts;
   DevBuf<double> d_xyz; // scattered model: the sample positions once more, SoA [3][npts] (the candidate scans read only these)
   DevBuf<int> d_cells;
   DevBuf<double> d_coef;
+  DevBuf<InterpModel> d_axes; // node-table layout: the axes in InterpModel's form (no table), for ray_keys_kernel
   DevBytes d_model; // device copy of the host struct (kernels read it through scalar loads)
   template <class M> const M *on_device() const { return (const M *)d_model.p; }
   // Allocated ONCE, in model_finish, and never reallocated: modelnum 7's struct holds a device pointer into it
@@ -276,7 +278,9 @@ static void launch_wave_blocks(K kernel, long long n, hipStream_t st, Args... ar
 // The one place that turns a kind number into a type: f is a generic callable and gets a ModelTag -- the model's struct, whether
 // its lookups use the wave's LDS tile, and how many one-wave blocks per CU the persistent grid of its trace launch has (interp:
 // 34 KiB of LDS per wave, 512 registers per lane: one wave per SIMD; scattered: 18.5 KiB, <= 256 registers: WAVES_PER_EU per
-// SIMD; ngo3d, simple3d and at64thch: as Ngo, whose integrator fills the default WaveBudget whatever the density body needs).
+// SIMD; ngo3d, simple3d and at64thch: as Ngo, whose integrator fills the default WaveBudget whatever the density body needs;
+// the interp model's node-table layout: no LDS, a lane's gathered values and coefficients in registers, 512 of them: one wave
+// per SIMD).
 template <class M, bool LDS, int WAVES_PER_CU>
 struct ModelTag {
   using Model = M;
@@ -292,6 +296,7 @@ static int with_model(const srt_model *m, F &&f) {
   case KIND_NGO3D: return f(ModelTag<Ngo3dModel, false, 8>{});
   case KIND_SIMPLE3D: return f(ModelTag<Simple3dModel, false, 8>{});
   case KIND_AT64THCH: return f(ModelTag<At64ThChModel, false, 8>{});
+  case KIND_INTERP_NODES: return f(ModelTag<InterpNodesModel, false, 4>{});
   }
   return srt_set_error(SRT_EINVAL, "model kind %d unsupported", m->kind);
 }
@@ -432,8 +437,12 @@ extern "C" int srt_model_set_tsyganenko_params(srt_model *m, const double parmod
   m->have_parmod = true;
   return upload_constants(m);
 }
-extern "C" int srt_model_kind(const srt_model *m) { return m ? m->kind : 0; }
+extern "C" int srt_model_kind(const srt_model *m) { return m ? (m->kind == KIND_INTERP_NODES ? (int)KIND_INTERP : m->kind) : 0; }
+extern "C" int srt_model_interp_layout(const srt_model *m) {
+  return !m ? -1 : m->kind == KIND_INTERP ? SRT_INTERP_EXPANDED : m->kind == KIND_INTERP_NODES ? SRT_INTERP_NODES : -1;
+}
 extern "C" int srt_model_nspec(const srt_model *m) { return m ? m->nspec : 0; }
+extern "C" const void *srt_model_device_struct(const srt_model *m) { return m ? m->d_model.p : nullptr; }
 extern "C" int64_t srt_model_device_bytes(const srt_model *m) { return m ? m->device_bytes : 0; }
 extern "C" int srt_model_species(const srt_model *m, double qs[SRT_MAXSPEC], double ms[SRT_MAXSPEC]) {
   if (!m) return srt_set_error(SRT_EINVAL, "null model");
@@ -669,17 +678,75 @@ __global__ __launch_bounds__(64) void build_coeffs_kernel(GridDims g, ArrPtrs ar
     b[t] = zero ? 0.0 : v;
     __syncthreads();
     double acc = 0.0;
-    for (int e = c_tri_ptr[t]; e < c_tri_ptr[t + 1]; ++e) acc += (double)c_tri_val[e] * b[(int)c_tri_col[e]];
+    for (int e = c_tri_ptr[t]; e < c_tri_ptr[t + 1]; ++e) acc = tri_term(acc, c_tri_val[e], b[(int)c_tri_col[e]]);
     coef[(size_t)pair * 64 + t] = acc;
   }
 }
 
-// FD derivatives (unless given) + coefficient expansion + model object, from the 8 arrays already on the device.
+// The node table of the second layout (srt_interp_nodes.hpp): nodes[node][species][8] = the eight constraint families of
+// build_coeffs_kernel, scaled by the spacings with its left-to-right products, so the stored bits are the bits it forms.
+// One thread per (node, species); the arrays and the table are indexed alike (gidx).
+__global__ void build_nodes_kernel(ArrPtrs arrs, double dx, double dy, double dz, double *nodes, size_t n) {
+  for (size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (size_t)gridDim.x * blockDim.x) {
+    double v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = arrs.a[q][id];
+    v[1] = v[1] * dx;
+    v[2] = v[2] * dy;
+    v[3] = v[3] * dz;
+    v[4] = v[4] * dx * dy;
+    v[5] = v[5] * dx * dz;
+    v[6] = v[6] * dy * dz;
+    v[7] = v[7] * dx * dy * dz;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) nodes[id * 8 + q] = v[q];
+  }
+}
+
+// ---- the two layouts of modelnum 3: sizes, and the choice SRT_INTERP_AUTO makes (pure host code) ----
+static bool layout_known(int layout) { return layout == SRT_INTERP_EXPANDED || layout == SRT_INTERP_NODES || layout == SRT_INTERP_AUTO; }
+static int layout_unknown(const char *who, int layout) {
+  return srt_set_error(SRT_EINVAL, "%s: unknown layout %d (SRT_INTERP_EXPANDED 0, SRT_INTERP_NODES 1, SRT_INTERP_AUTO 2)", who, layout);
+}
+extern "C" int srt_interp_layout_bytes(int nspec, int nx, int ny, int nz, int layout, int64_t *table, int64_t *peak) {
+  if (layout != SRT_INTERP_EXPANDED && layout != SRT_INTERP_NODES)
+    return srt_set_error(SRT_EINVAL, "srt_interp_layout_bytes: layout %d is neither SRT_INTERP_EXPANDED nor SRT_INTERP_NODES", layout);
+  if (nspec < 1 || nspec > SRT_MAXSPEC || nx < 2 || ny < 2 || nz < 2) return srt_set_error(SRT_EINVAL, "srt_interp_layout_bytes: bad grid");
+  const int64_t n = (int64_t)nx * ny * nz * nspec; // values per grid array
+  const int64_t t = layout == SRT_INTERP_EXPANDED ? (int64_t)(nx + 1) * (ny + 1) * (nz + 1) * nspec * 64 * 8 : n * 64;
+  if (table) *table = t;
+  if (peak) *peak = t + 8 * n * 8; // creation holds the eight grid arrays and the table at the same time
+  return SRT_OK;
+}
+extern "C" int srt_interp_layout_choose(int nspec, int nx, int ny, int nz, int64_t free_bytes) {
+  int64_t t, pk;
+  int rc = srt_interp_layout_bytes(nspec, nx, ny, nz, SRT_INTERP_EXPANDED, &t, &pk);
+  if (rc) return rc;
+  if (pk <= free_bytes) return SRT_INTERP_EXPANDED;
+  if ((rc = srt_interp_layout_bytes(nspec, nx, ny, nz, SRT_INTERP_NODES, &t, &pk))) return rc;
+  if (pk <= free_bytes) return SRT_INTERP_NODES;
+  return srt_set_error(SRT_ENOMEM, "interp model %dx%dx%d, %d species: the node table needs %lld bytes at creation, %lld are free", nx,
+                       ny, nz, nspec, (long long)pk, (long long)free_bytes);
+}
+// SRT_INTERP_AUTO -> the layout that fits the current device's free memory (or an error); the others pass through
+static int resolve_layout(int nspec, int nx, int ny, int nz, int layout, int *out) {
+  *out = layout;
+  if (layout != SRT_INTERP_AUTO) return SRT_OK;
+  size_t fr = 0, tot = 0;
+  HIP_OK(hipMemGetInfo(&fr, &tot));
+  const int c = srt_interp_layout_choose(nspec, nx, ny, nz, (int64_t)fr);
+  if (c < 0) return c;
+  *out = c;
+  return SRT_OK;
+}
+
+// FD derivatives (unless given) + coefficient expansion (or the node table: `layout`, SRT_INTERP_EXPANDED or _NODES) + model
+// object, from the 8 arrays already on the device.
 // arr[0] = F; arr[1..7] = derivative blocks (contents ignored when !have_derivs).  The arrays are freed here, before the model
 // is made.
 static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const double bounds[6], const double *qs,
                                      const double *ms, DevBuf<double> (&arr)[8], bool have_derivs, int yearday, int msec,
-                                     srt_model **out) {
+                                     srt_model **out, int layout = SRT_INTERP_EXPANDED) {
   const size_t nnode = (size_t)nx * ny * nz, n = nnode * nspec;
   const size_t ncell = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
   GridDims g{nspec, nx, ny, nz};
@@ -704,9 +771,46 @@ static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const do
     if (ny > 2 && nz > 2) fd(3, 6, 1, dy);
     if (nx > 2 && ny > 2 && nz > 2) fd(6, 7, 0, dx);
   }
-  if (e == hipSuccess) e = coef.alloc(ncell * nspec * 64);
+  const bool as_nodes = layout == SRT_INTERP_NODES;
+  if (e == hipSuccess) e = coef.alloc(as_nodes ? n * 8 : ncell * nspec * 64);
   if (e != hipSuccess)
     return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "interp model setup: %s", hipGetErrorString(e));
+  if (as_nodes) {
+    ArrPtrs ap;
+    for (int a = 0; a < 8; ++a) ap.a[a] = arr[a].p;
+    const int blocks = (int)((n + 255) / 256 < 65535 * 4 ? (n + 255) / 256 : 65535 * 4);
+    hipLaunchKernelGGL(build_nodes_kernel, dim3(blocks), dim3(256), 0, 0, ap, dx, dy, dz, coef.p, n);
+    e = hipDeviceSynchronize();
+    for (auto &b : arr) b.release();
+    if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "node table build failed: %s", hipGetErrorString(e));
+    srt_model *m = new srt_model;
+    m->kind = KIND_INTERP_NODES;
+    m->nspec = nspec;
+    m->d_coef.swap(coef);
+    m->device_bytes = (int64_t)(n * 8 * sizeof(double));
+    InterpNodesModel &nm = m->as<InterpNodesModel>();
+    nm.nodes = m->d_coef.p;
+    nm.nspec = nspec;
+    nm.ax = Axis{bounds[0], dx, 1.0 / dx, nx};
+    nm.ay = Axis{bounds[2], dy, 1.0 / dy, ny};
+    nm.az = Axis{bounds[4], dz, 1.0 / dz, nz};
+    // the launch-cell ray order (srt_trace_batch_device) takes its keys from the axes in InterpModel's form, on both layouts
+    InterpModel &im = m->as<InterpModel>();
+    im.coef = nullptr;
+    im.nspec = nspec;
+    im.ax = nm.ax, im.ay = nm.ay, im.az = nm.az;
+    fill_common(m->cm, nspec, qs, ms, yearday, msec);
+    int rc = model_finish(m);
+    if (!rc && m->d_axes.alloc(1) != hipSuccess) rc = srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+    if (!rc && hipMemcpy(m->d_axes.p, &im, sizeof im, hipMemcpyHostToDevice) != hipSuccess)
+      rc = srt_set_error(SRT_EDEVICE, "upload of the axes failed");
+    if (rc) {
+      srt_model_destroy(m);
+      return rc;
+    }
+    *out = m;
+    return SRT_OK;
+  }
   (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_ptr), TRI_PTR, sizeof TRI_PTR);
   (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_col), TRI_COL, sizeof TRI_COL);
   (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_val), TRI_VAL, sizeof TRI_VAL);
@@ -746,9 +850,8 @@ static int alloc_grid_arrays(size_t n, DevBuf<double> (&arr)[8]) {
   return SRT_OK;
 }
 
-extern "C" int srt_model_create_interp(int nspec, int nx, int ny, int nz, const double bounds[6],
-                                       const double *qs, const double *ms, const double *F,
-                                       const double *const *derivs, int yearday, int msec, srt_model **out) {
+static int create_interp(int nspec, int nx, int ny, int nz, const double bounds[6], const double *qs, const double *ms,
+                         const double *F, const double *const *derivs, int yearday, int msec, int layout, srt_model **out) {
   if (!bounds || !qs || !ms || !F || !out) return srt_set_error(SRT_EINVAL, "null argument");
   if (nspec < 1 || nspec > SRT_MAXSPEC)
     return srt_set_error(SRT_EINVAL, "nspec=%d unsupported (1..%d species: SRT_MAXSPEC, include/srt.h)", nspec, SRT_MAXSPEC);
@@ -758,6 +861,7 @@ extern "C" int srt_model_create_interp(int nspec, int nx, int ny, int nz, const 
   if (rc) return rc;
   const size_t n = (size_t)nx * ny * nz * nspec;
   if ((size_t)(nx + 1) * (ny + 1) * (nz + 1) >= (size_t)1 << 31) return srt_set_error(SRT_EINVAL, "grid too large");
+  if ((rc = resolve_layout(nspec, nx, ny, nz, layout, &layout))) return rc;
   DevBuf<double> arr[8];
   rc = alloc_grid_arrays(n, arr);
   if (rc) return rc;
@@ -766,7 +870,18 @@ extern "C" int srt_model_create_interp(int nspec, int nx, int ny, int nz, const 
     for (int a = 1; a < 8 && e == hipSuccess; ++a)
       e = hipMemcpy(arr[a].p, derivs[a - 1], n * sizeof(double), hipMemcpyHostToDevice);
   if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "grid upload: %s", hipGetErrorString(e));
-  return interp_from_device_arrays(nspec, nx, ny, nz, bounds, qs, ms, arr, derivs != nullptr, yearday, msec, out);
+  return interp_from_device_arrays(nspec, nx, ny, nz, bounds, qs, ms, arr, derivs != nullptr, yearday, msec, out, layout);
+}
+extern "C" int srt_model_create_interp(int nspec, int nx, int ny, int nz, const double bounds[6],
+                                       const double *qs, const double *ms, const double *F,
+                                       const double *const *derivs, int yearday, int msec, srt_model **out) {
+  return create_interp(nspec, nx, ny, nz, bounds, qs, ms, F, derivs, yearday, msec, SRT_INTERP_EXPANDED, out);
+}
+extern "C" int srt_model_create_interp_layout(int nspec, int nx, int ny, int nz, const double bounds[6], const double *qs,
+                                              const double *ms, const double *F, const double *const *derivs, int yearday,
+                                              int msec, int layout, srt_model **out) {
+  if (!layout_known(layout)) return layout_unknown("srt_model_create_interp_layout", layout);
+  return create_interp(nspec, nx, ny, nz, bounds, qs, ms, F, derivs, yearday, msec, layout, out);
 }
 
 // ---- the step before the path: sample a model on a regular grid, in log space, on the device ----
@@ -910,29 +1025,47 @@ extern "C" int srt_build_grid(srt_model *src, int compder, int nx, int ny, int n
   return SRT_OK;
 }
 
-extern "C" int srt_model_create_interp_from_model(srt_model *src, int compder, int nx, int ny, int nz,
-                                                  const double bounds[6], int yearday, int msec, srt_model **out) {
+static int create_interp_from_model(srt_model *src, int compder, int nx, int ny, int nz, const double bounds[6], int yearday,
+                                    int msec, int layout, srt_model **out) {
   int rc = check_grid_request(src, nx, ny, nz, bounds);
   if (rc) return rc;
   if (!out) return srt_set_error(SRT_EINVAL, "null argument");
   SRT_MODEL_SCOPE; // the new model is built beside its source, on the source's device
   if ((rc = ensure_model(src))) return rc;
   const size_t n = (size_t)nx * ny * nz * src->nspec;
+  if ((rc = resolve_layout(src->nspec, nx, ny, nz, layout, &layout))) return rc;
   DevBuf<double> arr[8];
   if ((rc = alloc_grid_arrays(n, arr)) || (rc = sample_model_on_grid(src, compder ? 1 : 0, nx, ny, nz, bounds, arr))) return rc;
   return interp_from_device_arrays(src->nspec, nx, ny, nz, bounds, src->cm.sp.q, src->cm.sp.m, arr, compder != 0,
-                                   yearday, msec, out);
+                                   yearday, msec, out, layout);
+}
+extern "C" int srt_model_create_interp_from_model(srt_model *src, int compder, int nx, int ny, int nz,
+                                                  const double bounds[6], int yearday, int msec, srt_model **out) {
+  return create_interp_from_model(src, compder, nx, ny, nz, bounds, yearday, msec, SRT_INTERP_EXPANDED, out);
+}
+extern "C" int srt_model_create_interp_from_model_layout(srt_model *src, int compder, int nx, int ny, int nz,
+                                                         const double bounds[6], int yearday, int msec, int layout,
+                                                         srt_model **out) {
+  if (!layout_known(layout)) return layout_unknown("srt_model_create_interp_from_model_layout", layout);
+  return create_interp_from_model(src, compder, nx, ny, nz, bounds, yearday, msec, layout, out);
 }
 
-extern "C" int srt_model_create_interp_file(const char *gridfile, int yearday, int msec, srt_model **out) {
+static int create_interp_file(const char *gridfile, int yearday, int msec, int layout, srt_model **out) {
   if (!gridfile || !out) return srt_set_error(SRT_EINVAL, "null argument");
   srt_host::GridFile gf;
   std::string err;
   if (!srt_host::read_grid_file(gridfile, gf, err)) return srt_set_error(SRT_EIO, "%s: %s", gridfile, err.c_str());
   const double *dptr[7];
   for (int a = 0; a < 7; ++a) dptr[a] = gf.have_derivs ? gf.derivs[a].data() : nullptr;
-  return srt_model_create_interp(gf.nspec, gf.nx, gf.ny, gf.nz, gf.bounds, gf.qs, gf.ms, gf.F.data(),
-                                 gf.have_derivs ? dptr : nullptr, yearday, msec, out);
+  return create_interp(gf.nspec, gf.nx, gf.ny, gf.nz, gf.bounds, gf.qs, gf.ms, gf.F.data(), gf.have_derivs ? dptr : nullptr, yearday,
+                       msec, layout, out);
+}
+extern "C" int srt_model_create_interp_file(const char *gridfile, int yearday, int msec, srt_model **out) {
+  return create_interp_file(gridfile, yearday, msec, SRT_INTERP_EXPANDED, out);
+}
+extern "C" int srt_model_create_interp_file_layout(const char *gridfile, int yearday, int msec, int layout, srt_model **out) {
+  if (!layout_known(layout)) return layout_unknown("srt_model_create_interp_file_layout", layout);
+  return create_interp_file(gridfile, yearday, msec, layout, out);
 }
 
 extern "C" int srt_model_create_scattered_file(const char *ptsfile, int yearday, int msec, double window_scale,
@@ -1538,7 +1671,7 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   srt_model::LaunchTimes &lt = m->hist[m->next_hist];
   HIP_OK(hipEventRecord(lt.ev0, st));
   const InterpModel &im = m->as<InterpModel>();
-  if (p->ray_order >= 1 && m->kind == KIND_INTERP && nrays > WAVE && nrays < (1ll << 31) && im.ax.n < 1023 && im.ay.n < 1023 &&
+  if (p->ray_order >= 1 && (m->kind == KIND_INTERP || m->kind == KIND_INTERP_NODES) && nrays > WAVE && nrays < (1ll << 31) && im.ax.n < 1023 && im.ay.n < 1023 &&
       im.az.n < 1023) {
     // work through the launch set in the order of the rays' launch cells (inside the timed region)
     if ((size_t)nrays > sl.ids[1].cap) {
@@ -1560,7 +1693,8 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
       if (sl.used) HIP_OK(hipEventSynchronize(sl.done));
       HIP_OK(sl.sorttmp.alloc(need));
     }
-    hipLaunchKernelGGL(ray_keys_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, st, m->on_device<InterpModel>(), d_pos0,
+    hipLaunchKernelGGL(ray_keys_kernel, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, st,
+                       m->kind == KIND_INTERP ? m->on_device<InterpModel>() : (const InterpModel *)m->d_axes.p, d_pos0,
                        d_dir0, d_w0, p->ray_order == 2 ? 1 : 0, (long long)nrays, sl.keys[0].p, sl.ids[0].p);
     size_t tb = sl.sorttmp.cap;
     HIP_OK(hipcub::DeviceRadixSort::SortPairs(sl.sorttmp.p, tb, sl.keys[0].p, sl.keys[1].p, sl.ids[0].p, sl.ids[1].p, (int)nrays, 0, 31, st));

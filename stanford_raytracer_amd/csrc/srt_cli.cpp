@@ -91,8 +91,20 @@ static int make_model(int device, srt_model **out, double *del) {
   } else if (modelnum == 3) {
     need(getopt_named("interp_interpfile", file), "interp_interpfile");
     p.del = 1.0e-6;
+    // ours: --interp_layout=expanded|nodes|auto, the device layout of the table (include/srt.h); default expanded
+    int layout = SRT_INTERP_EXPANDED;
+    std::string lay;
+    if (getopt_named("interp_layout", lay)) {
+      if (lay == "expanded") layout = SRT_INTERP_EXPANDED;
+      else if (lay == "nodes") layout = SRT_INTERP_NODES;
+      else if (lay == "auto") layout = SRT_INTERP_AUTO;
+      else {
+        fprintf(stderr, "raytracer: --interp_layout=%s is not a layout (expanded, nodes or auto)\n", lay.c_str());
+        exit(2);
+      }
+    }
     printf(" Reading input file\n");
-    CHECK(srt_model_create_interp_file(file.c_str(), yearday, msec, &m));
+    CHECK(srt_model_create_interp_file_layout(file.c_str(), yearday, msec, layout, &m));
     printf(" Done\n");
   } else if (modelnum == 4) {
     need(getopt_named("interp_interpfile", file), "interp_interpfile");
@@ -172,6 +184,7 @@ int main(int argc, char **argv) {
          "              (6) simplified GCPM (closed form)  (7) AT64ThCh (one field-line trace per evaluated point)\n"
          "  model 1: --ngo_configfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1 --tsyganenko_Pdyn .. _W6\n"
          "  model 3: --interp_interpfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1\n"
+         "           [--interp_layout=expanded|nodes|auto: the table on the device; nodes = an eighth of the bytes, slower]\n"
          "  model 4: model 3 flags + --scattered_interp_window_scale --scattered_interp_order\n"
          "           --scattered_interp_exact --scattered_interp_local_window_scale\n"
          "           [--scattered_interp_root_sample=N: record N of the file is the root of the reference's kd-tree (spacing 0)]\n"

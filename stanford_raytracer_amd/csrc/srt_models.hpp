@@ -477,7 +477,7 @@ struct InterpModel {
   // nested Horner, coefficient-outer / point-inner so each coefficient is read once.
   // chunk(q) returns coefficients (2q, 2q+1).
   template <int NP, class Chunk>
-  __device__ __forceinline__ static void eval(Chunk chunk, const double (&x)[NP], const double (&y)[NP],
+  SRT_HD __forceinline__ static void eval(Chunk chunk, const double (&x)[NP], const double (&y)[NP],
                                               const double (&z)[NP], double (&out)[NP]) {
     double vz[NP];
 #pragma unroll

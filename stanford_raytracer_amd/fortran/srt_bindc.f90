@@ -9,6 +9,8 @@ module srt_bindc
   use iso_c_binding
   implicit none
   integer, parameter :: SRT_ROW = 20, SRT_MAXSPEC = 4
+  ! device layouts of the interp model (include/srt.h)
+  integer(c_int), parameter :: SRT_INTERP_EXPANDED = 0, SRT_INTERP_NODES = 1, SRT_INTERP_AUTO = 2
 
   type, bind(C) :: srt_params
      real(c_double) :: dt0, dtmax, tmax, maxerr, minalt, del
@@ -43,6 +45,47 @@ module srt_bindc
        integer(c_int), value :: yearday, msec
        type(c_ptr) :: model
      end function srt_model_create_interp_file
+     ! modelnum = 3 in a chosen device layout (SRT_INTERP_EXPANDED / _NODES / _AUTO above; include/srt.h): from a grid file,
+     ! from host arrays F(nspec,nx,ny,nz) (derivs = c_null_ptr or the address of seven c_ptr to arrays of F's shape), from
+     ! another handle; the layout a handle has (-1: not an interp model); and the two pure host functions on the sizes
+     integer(c_int) function srt_model_create_interp_file_layout(gridfile, yearday, msec, layout, model) &
+          bind(C, name="srt_model_create_interp_file_layout")
+       import :: c_int, c_char, c_ptr
+       character(kind=c_char), dimension(*) :: gridfile
+       integer(c_int), value :: yearday, msec, layout
+       type(c_ptr) :: model
+     end function srt_model_create_interp_file_layout
+     integer(c_int) function srt_model_create_interp_layout(nspec, nx, ny, nz, bounds, qs, ms, F, derivs, yearday, msec, &
+          layout, model) bind(C, name="srt_model_create_interp_layout")
+       import :: c_int, c_ptr, c_double
+       integer(c_int), value :: nspec, nx, ny, nz, yearday, msec, layout
+       real(c_double), intent(in) :: bounds(6), qs(*), ms(*), F(*)
+       type(c_ptr), value :: derivs
+       type(c_ptr) :: model
+     end function srt_model_create_interp_layout
+     integer(c_int) function srt_model_create_interp_from_model_layout(src, compder, nx, ny, nz, bounds, yearday, msec, &
+          layout, model) bind(C, name="srt_model_create_interp_from_model_layout")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: src
+       integer(c_int), value :: compder, nx, ny, nz, yearday, msec, layout
+       real(c_double), intent(in) :: bounds(6)
+       type(c_ptr) :: model
+     end function srt_model_create_interp_from_model_layout
+     integer(c_int) function srt_model_interp_layout(model) bind(C, name="srt_model_interp_layout")
+       import :: c_int, c_ptr
+       type(c_ptr), value :: model
+     end function srt_model_interp_layout
+     integer(c_int) function srt_interp_layout_bytes(nspec, nx, ny, nz, layout, table, peak) &
+          bind(C, name="srt_interp_layout_bytes")
+       import :: c_int, c_int64_t
+       integer(c_int), value :: nspec, nx, ny, nz, layout
+       integer(c_int64_t) :: table, peak
+     end function srt_interp_layout_bytes
+     integer(c_int) function srt_interp_layout_choose(nspec, nx, ny, nz, free_bytes) bind(C, name="srt_interp_layout_choose")
+       import :: c_int, c_int64_t
+       integer(c_int), value :: nspec, nx, ny, nz
+       integer(c_int64_t), value :: free_bytes
+     end function srt_interp_layout_choose
      ! modelnum = 5 (ngo_3d_dens_model_adapter.f95): the Ngo model with the plasmapause of each point at a8(MLT, kp) - ddk;
      ! fixed_MLT = 1 holds every point at MLT hours (the reference's driver never sets it)
      integer(c_int) function srt_model_create_ngo3d(configfile, kp, fixed_MLT, MLT, yearday, msec, model) &
