@@ -267,6 +267,24 @@ int srt_rk_step(srt_model *m, int64_t n, const double *args, const double *dt, d
  * Works on a handle of any kind whose coefficient table is loaded (srt_model_set_field with use_igrf or use_tsyganenko, or a
  * modelnum-7 handle) and whose parmod is set (srt_model_set_tsyganenko_params, or a modelnum-7 handle): SRT_EINVAL otherwise. */
 int srt_field_line_foot(srt_model *m, int64_t n, const double *x, double *out);
+/* dumpmodel.f95: f[nz][ny][nx][4*nspec+3] = (qs, Ns, ms, nus, B0) of every node; file order (the Fortran's
+ * f(:,i,j,k)).  Any of nx, ny, nz may be 1 (that axis sits at its minimum, as the Fortran's linspace does).
+ * mag_coords = 1: each node goes through sm_to_mag_d for the model's date before the model sees it.
+ * The nodes are formed on the device as the Fortran forms them, x(i) = i*del + min with del = (max - min)/(n - 1.0), and every
+ * node's record is what srt_plasma_params returns at its coordinates (at srt_sm_to_mag of them for mag_coords = 1), bit for
+ * bit, less the unused species slot: nspec = srt_model_nspec, 3 for modelnum 7 and 4 otherwise.  nus is all zeros, as in every
+ * adapter of the reference.  The reference's dumpmodel reads --mag_coords for modelnum 6 and 7 only and leaves the variable
+ * unset when the flag is absent (its toolchain zeroes it): DEFINED BEHAVIOUR here is that the caller always says 0 or 1, that an
+ * absent flag is 0 (SM), and that the rotation is applied to a handle of any kind when asked for.
+ * SRT_EINVAL, by name: an axis with fewer than 1 node, empty bounds (max <= min) on an axis of more than one node, more than
+ * 2^31 - 1 nodes, mag_coords other than 0 or 1.  SRT_ENOMEM: the output does not fit on the device.
+ * srt_last_kernel_ms afterwards gives the duration of the dump's launches. */
+int srt_dump_model(srt_model *m, int nx, int ny, int nz, const double bounds[6], int mag_coords, double *f);
+/* SM -> MAG (inverse = 0) or MAG -> SM (inverse = 1) for x[n][3], xform_double's sm_to_mag_d / mag_to_sm_d for
+ * itime = (yearday, msec): seven plane rotations about the dipole tilt, the GSM, GSE, GEI and GEO angles of the date and the
+ * pole's position, applied one after the other in the Fortran's order and arithmetic.  Pure host code, needs no GPU; the
+ * device applies the same rotations, from the same sines and cosines, in srt_dump_model. */
+int srt_sm_to_mag(int yearday, int msec, int inverse, int64_t n, const double *x, double *out);
 
 /* ---- the hot path: replaces the driver's whole ray loop ---- */
 /* slots per ray = ceil(maxsteps/outputper) */
@@ -304,8 +322,8 @@ int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t nrays, con
 int srt_pack_rows_device(int32_t slots, int32_t outputper, int64_t nrays, const double *d_rows,
                          const int32_t *d_nrows, int64_t *d_offsets, double *d_packed, int64_t capacity_rows,
                          void *stream);
-/* duration in ms of the most recent trace kernel on this model, measured with HIP events on the
- * stream it ran on (synchronises that stream) */
+/* duration in ms of the most recent trace kernel on this model (or of the launches of the most recent srt_dump_model), measured
+ * with HIP events on the stream it ran on (synchronises that stream) */
 int srt_last_kernel_ms(srt_model *m, float *ms);
 /* the same for the launch `back` launches before the most recent one (0 .. 3): lets a caller that keeps several
  * launches in flight on different streams read their durations afterwards */
@@ -381,6 +399,14 @@ int srt_points_file_write(const char *path, int binary, int nspec, int64_t npts,
                           const double *qs, const double *ms, const double *records);
 int srt_points_file_convert(const char *in_text, const char *out_binary);
 int srt_points_file_is_binary(const char *path);
+
+/* dump files, the output of the reference's dumpmodel (dumpmodel.f95:1284-1292) and of srt_dump_model: one (5i10) record
+ * nspec nx ny nz, one (6es24.15e3) record minx maxx miny maxy minz maxz, then every value of f[nz][ny][nx][4*nspec+3] on a
+ * line of its own, (es24.15e3), in array order.  The writer is byte-exact against the reference.  The reader returns
+ * dims = {nspec, nx, ny, nz} and a malloc'd *f (srt_free) and refuses (SRT_EIO) a file whose value count is not the
+ * (4 nspec + 3) nx ny nz of its header.  Text only.  Pure host code, needs no GPU. */
+int srt_dump_file_write(const char *path, int nspec, int nx, int ny, int nz, const double bounds[6], const double *f);
+int srt_dump_file_read(const char *path, int32_t dims[4] /* nspec nx ny nz */, double bounds[6], double **f /* srt_free */);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,10 @@ def lib():
     L.srt_points_file_write.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int64, dp, dp, dp, dp]
     L.srt_points_file_convert.argtypes = [C.c_char_p, C.c_char_p]
     L.srt_points_file_is_binary.argtypes = [C.c_char_p]
+    L.srt_dump_model.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp]
+    L.srt_sm_to_mag.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, dp, dp]
+    L.srt_dump_file_write.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp]
+    L.srt_dump_file_read.argtypes = [C.c_char_p, i32p, dp, C.POINTER(dp)]
     _lib = L
     return L
 
@@ -309,6 +313,15 @@ class Model:
         _check(lib().srt_build_grid(self.h, int(bool(compder)), nx, ny, nz, _dp(_f64(bounds, (6,))), _dp(F),
                                     _dp(D) if compder else None))
         return F, (list(D) if compder else None)
+
+    def dump(self, nx, ny, nz, bounds, mag_coords=False):
+        """The reference's dumpmodel on the device: funcPlasmaParams at every node of a regular grid (any axis may have one
+        node: a slice).  -> f[nz, ny, nx, 4*nspec+3] = qs, Ns, ms, nus (all zeros), B0 of the node, the dump file's order.
+        mag_coords: the grid is in MAG (geomagnetic dipole) coordinates; each node goes through sm_to_mag for the model's date
+        first, as dumpmodel.f95 does.  Every node is bit-equal to plasma_params at its coordinates."""
+        f = np.empty((nz, ny, nx, 4 * self.nspec + 3))
+        _check(lib().srt_dump_model(self.h, nx, ny, nz, _dp(_f64(bounds, (6,))), int(mag_coords), _dp(f)))
+        return f
 
     def build_samples(self, bounds, n_zero_altitude=0, n_iri_pad=0, n_initial_radial=0, n_initial_uniform=0,
                       adaptive_nmax=0, initial_tol=1.0, max_recursion=20, numincrease=5, max_passes=0, seed=0,
@@ -573,6 +586,38 @@ def convert_grid_file(src, dst_binary):
 
 def grid_file_is_binary(path):
     return bool(lib().srt_grid_file_is_binary(path.encode()))
+
+
+def sm_to_mag(x, yearday, msec, inverse=False):
+    """xform_double's sm_to_mag_d (inverse: mag_to_sm_d) for x[n,3] at itime = (yearday, msec); host code, no GPU."""
+    x = _f64(x, (-1, 3))
+    out = np.empty_like(x)
+    _check(lib().srt_sm_to_mag(int(yearday), int(msec), int(bool(inverse)), x.shape[0], _dp(x), _dp(out)))
+    return out
+
+
+# ---- dump files: the output of the reference's dumpmodel and of Model.dump (host code, no GPU) -------
+def write_dump_file(path, f, bounds):
+    """f[nz, ny, nx, 4*nspec+3] as Model.dump returns it -> the text file dumpmodel.f95 writes, byte for byte."""
+    f = _f64(f)
+    nz, ny, nx, per = f.shape
+    if per % 4 != 3:
+        raise ValueError("the last axis holds 4*nspec+3 values, not %d" % per)
+    _check(lib().srt_dump_file_write(os.fsencode(path), (per - 3) // 4, nx, ny, nz, _dp(_f64(bounds, (6,))), _dp(f)))
+
+
+def read_dump_file(path):
+    """-> dict(f[nz, ny, nx, 4*nspec+3], bounds[6], nspec)."""
+    dims = (C.c_int32 * 4)()
+    bounds = np.zeros(6)
+    pf = dp()
+    _check(lib().srt_dump_file_read(os.fsencode(path), dims, _dp(bounds), C.byref(pf)))
+    nspec, nx, ny, nz = (int(v) for v in dims)
+    try:
+        f = np.ctypeslib.as_array(pf, shape=(nz * ny * nx * (4 * nspec + 3),)).copy().reshape(nz, ny, nx, 4 * nspec + 3)
+    finally:
+        lib().srt_free(pf)
+    return {"f": f, "bounds": bounds, "nspec": nspec}
 
 
 def write_points_file(path, records, bounds, qs, ms, binary=False):

@@ -28,6 +28,7 @@
 #include "srt_at64thch.hpp"
 #include "srt_sampler.hpp"
 #include "srt_damping.hpp"
+#include "srt_xform.hpp"
 #include <hipcub/hipcub.hpp>
 
 using namespace srt;
@@ -1022,6 +1023,109 @@ extern "C" int srt_build_grid(srt_model *src, int compder, int nx, int ny, int n
     for (int a = 1; a < 8 && e == hipSuccess; ++a)
       e = hipMemcpy(derivs + (size_t)(a - 1) * n, arr[a].p, n * sizeof(double), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "grid download: %s", hipGetErrorString(e));
+  return SRT_OK;
+}
+
+// ---- dumpmodel.f95: funcPlasmaParams of any model on a regular grid, in SM or MAG coordinates ----
+// Three launches on one stream: the nodes' coordinates (dumpmodel.f95:219-237, and SM_TO_MAG_D for mag_coords = 1,
+// :1140-1143), then the UNCHANGED params_kernel on them, then the 19 values of a node packed into the file's 4 nspec + 3.  The
+// dump of a node is therefore what srt_plasma_params gives at the node's coordinates, bit for bit, by construction: the
+// lookups are the same instruction stream on the same inputs (a kernel that formed the coordinates around the lookup would
+// leave the compiler free to fuse other products, HISTORY.md section 22).
+struct DumpArgs {
+  double min[3], del[3];
+  int n[3];
+  int mag;
+  xform::Chain chain;
+};
+// x[count][3] = the coordinates of nodes first .. first + count - 1 (linear index = the file's order: x fastest, then y, z)
+__global__ __launch_bounds__(256) void dump_points_kernel(DumpArgs A, long long first, long long count, double *__restrict__ x) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  const long long node = first + t;
+  const int idx[3] = {(int)(node % A.n[0]), (int)((node / A.n[0]) % A.n[1]), (int)(node / ((long long)A.n[0] * A.n[1]))};
+  double pos[3];
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double p = (double)idx[c] * A.del[c]; // (/ (ind) /)*del + min: a product, then a sum
+      pos[c] = A.n[c] == 1 ? A.min[c] : p + A.min[c]; // one node: x = (/ minx /), del (a quotient by zero) is never read
+    }
+  }
+  double q[3] = {pos[0], pos[1], pos[2]};
+  if (A.mag) xform::apply(A.chain, pos, q);
+  x[3 * t] = q[0];
+  x[3 * t + 1] = q[1];
+  x[3 * t + 2] = q[2];
+}
+// f[count][4 nspec + 3] = (qs, Ns, ms, nus, B0) from params_kernel's p[count][19] = qs(4) Ns(4) ms(4) nus(4) B0(3): the unused
+// species slot of a three-species model is dropped.  One thread per output value: a block writes one contiguous run.
+__global__ __launch_bounds__(256) void dump_pack_kernel(long long count, int nspec, const double *__restrict__ p, double *__restrict__ f) {
+  const int per = 4 * nspec + 3;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count * per) return;
+  const long long node = t / per;
+  const int c = (int)(t - node * per);
+  const int src = c < 4 * nspec ? 4 * (c / nspec) + c % nspec : 16 + (c - 4 * nspec);
+  f[t] = p[19 * node + src];
+}
+
+extern "C" int srt_dump_model(srt_model *m, int nx, int ny, int nz, const double bounds[6], int mag_coords, double *f) {
+  // every refusal by name comes before the device is touched
+  if (!bounds || !f) return srt_set_error(SRT_EINVAL, "srt_dump_model: null argument");
+  if (nx < 1 || ny < 1 || nz < 1) return srt_set_error(SRT_EINVAL, "srt_dump_model: nx, ny, nz = %d, %d, %d: every axis needs at least 1 node", nx, ny, nz);
+  const int n3[3] = {nx, ny, nz};
+  for (int c = 0; c < 3; ++c)
+    if (n3[c] > 1 && !(bounds[2 * c + 1] > bounds[2 * c]))
+      return srt_set_error(SRT_EINVAL, "srt_dump_model: empty bounds on the %c axis (%d nodes need max > min)", "xyz"[c], n3[c]);
+  const long long nxy = (long long)nx * ny, nnode = nxy <= 2147483647ll ? nxy * nz : -1; // (either product fits 63 bits)
+  if (nnode < 0 || nnode > 2147483647ll)
+    return srt_set_error(SRT_EINVAL, "srt_dump_model: %d x %d x %d is more than 2^31 - 1 nodes", nx, ny, nz);
+  if (mag_coords != 0 && mag_coords != 1) return srt_set_error(SRT_EINVAL, "srt_dump_model: mag_coords = %d is neither 0 (SM) nor 1 (MAG)", mag_coords);
+  if (!m) return srt_set_error(SRT_EINVAL, "srt_dump_model: null model");
+  SRT_MODEL_SCOPE;
+  int rc = ensure_model(m);
+  if (rc) return rc;
+  DumpArgs A;
+  memset(&A, 0, sizeof A);
+  for (int c = 0; c < 3; ++c) {
+    A.n[c] = n3[c];
+    A.min[c] = bounds[2 * c];
+    A.del[c] = n3[c] > 1 ? (bounds[2 * c + 1] - bounds[2 * c]) / (n3[c] - 1.0) : 0.0; // dumpmodel.f95:220-222
+  }
+  A.mag = mag_coords;
+  if (mag_coords) A.chain = xform::chain(m->cm.fld.yearday, m->cm.fld.msec, false);
+  const int per = 4 * m->nspec + 3;
+  // the output is whole on the device; the coordinates and params_kernel's 19 values per node exist for one piece at a time
+  const long long PIECE = 1ll << 20;
+  const long long piece = nnode < PIECE ? nnode : PIECE;
+  DevBuf<double> dx, dp19, df;
+  if (df.alloc((size_t)nnode * per) != hipSuccess || dx.alloc((size_t)3 * piece) != hipSuccess || dp19.alloc((size_t)19 * piece) != hipSuccess) {
+    (void)hipGetLastError();
+    return srt_set_error(SRT_ENOMEM, "srt_dump_model: %lld nodes of %d values do not fit on the device", nnode, per);
+  }
+  srt_model::LaunchTimes &lt = m->hist[m->next_hist];
+  HIP_OK(hipEventRecord(lt.ev0, 0));
+  for (long long first = 0; first < nnode; first += piece) {
+    const long long count = nnode - first < piece ? nnode - first : piece;
+    hipLaunchKernelGGL(dump_points_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, A, first, count, dx.p);
+    rc = with_model(m, [&](auto tag) -> int {
+      using T = decltype(tag);
+      launch_wave_blocks(params_kernel<typename T::Model, T::lds>, count, 0, m->on_device<typename T::Model>(), m->d_common.p, count,
+                         (const double *)dx.p, dp19.p);
+      return SRT_OK;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(dump_pack_kernel, dim3((unsigned)((count * per + 255) / 256)), dim3(256), 0, 0, count, m->nspec,
+                       (const double *)dp19.p, df.p + (size_t)first * per);
+  }
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(lt.ev1, 0));
+  lt.used = true;
+  m->last_hist = m->next_hist;
+  m->next_hist = (m->next_hist + 1) % srt_model::NHIST;
+  HIP_OK(hipMemcpy(f, df.p, (size_t)nnode * per * sizeof(double), hipMemcpyDeviceToHost));
   return SRT_OK;
 }
 

@@ -203,6 +203,9 @@ int main(int argc, char **argv) {
          "           builder gcpm_dens_model_buildgrid with the model of --modelnum in place of GCPM; --binary=1)\n"
          "           --buildsamples=1 --filename=<out> --minx .. --maxz --n_initial_uniform ... (the reference's random grid\n"
          "           builder with the model of --modelnum in place of GCPM; --seed, --binary=1)\n"
+         "           --dumpmodel=1 --filename=<out> --minx .. --maxz --nx --ny --nz (the reference's dumpmodel: qs, Ns, ms, nus, B0\n"
+         "           of the model of --modelnum at every node; an axis may have one node; --mag_coords=1 with model 6 or 7: the\n"
+         "           grid is in MAG coordinates)\n"
          "           --damping_out=<file>: hot-plasma damping along the kept rows (raynum, row, t, rate, magnitude, flag);\n"
          "           with --damping_in=<.ray file> instead of tracing: along the records of an existing file");
     return 0;
@@ -300,6 +303,63 @@ int main(int argc, char **argv) {
       printf(" %lld samples: %lld radial, %lld uniform, %lld adaptive, %lld zero-altitude, %lld ionosphere\n", (long long)n,
              (long long)counts[1], (long long)counts[2], (long long)counts[3], (long long)counts[4], (long long)counts[5]);
       srt_free(rec);
+      srt_model_destroy(m);
+      return 0;
+    }
+  }
+  {
+    // the reference's dumpmodel (fortran/dumpmodel.f95): funcPlasmaParams of the model of --modelnum at every node of a regular
+    // grid, any axis of which may have one node.  Same flags (:167-213: --minx .. --maxz, --nx --ny --nz read as reals and
+    // floored, --filename; the model's flags as make_model reads them) and the same text (:1284-1292, srt_dump_file_write).
+    // --mag_coords (:1086-1091, :1238-1242) is read for modelnum 6 and 7 only, as there; absent = 0, the value the reference's
+    // toolchain leaves in the unset variable.  Ours: --device, --timing=1.
+    std::string flag;
+    if (getopt_named("dumpmodel", flag) && flag != "0") {
+      std::string out;
+      need(getopt_named("filename", out), "filename");
+      double b[6], v = 0;
+      const char *bn[6] = {"minx", "maxx", "miny", "maxy", "minz", "maxz"};
+      for (int k = 0; k < 6; ++k) need(get_real(bn[k], b[k]), bn[k]);
+      int n3[3] = {0, 0, 0}, device = 0, timing = 0, modelnum = 0, mag = 0;
+      const char *nn[3] = {"nx", "ny", "nz"};
+      for (int k = 0; k < 3; ++k) {
+        need(get_real(nn[k], v), nn[k]);
+        n3[k] = (int)floor(v);
+        if (!(v >= 1.0 && v < 2147483648.0)) {
+          fprintf(stderr, "raytracer: --%s must be >= 1 (one node = a slice: that axis sits at its minimum)\n", nn[k]);
+          return 2;
+        }
+      }
+      if ((double)n3[0] * n3[1] * n3[2] > 2147483647.0) {
+        fprintf(stderr, "raytracer: --nx x --ny x --nz is more than 2^31 - 1 nodes\n");
+        return 2;
+      }
+      get_int("device", device);
+      get_int("timing", timing);
+      get_int("modelnum", modelnum);
+      if (get_int("mag_coords", mag) && modelnum != 6 && modelnum != 7) {
+        fprintf(stderr, "raytracer: --mag_coords is read for --modelnum=6 and 7 only (as by the reference's dumpmodel); ignored for "
+                        "--modelnum=%d: the grid is in SM coordinates\n", modelnum);
+        mag = 0;
+      }
+      const double t0 = now_s();
+      srt_model *m = nullptr;
+      double del = 0.0;
+      int rc = make_model(device, &m, &del);
+      if (rc) return rc;
+      const double t1 = now_s();
+      const int nspec = srt_model_nspec(m);
+      std::vector<double> f((size_t)n3[0] * n3[1] * n3[2] * (4 * (size_t)nspec + 3));
+      CHECK(srt_dump_model(m, n3[0], n3[1], n3[2], b, mag, f.data()));
+      float kernel_ms = 0.f;
+      srt_last_kernel_ms(m, &kernel_ms);
+      const double t2 = now_s();
+      CHECK(srt_dump_file_write(out.c_str(), nspec, n3[0], n3[1], n3[2], b, f.data()));
+      const double t3 = now_s();
+      printf(" %d x %d x %d nodes, %d species, %s coordinates\n", n3[0], n3[1], n3[2], nspec, mag ? "MAG" : "SM");
+      if (timing)
+        printf(" timing: {\"model_s\": %.3f, \"dump_s\": %.3f, \"kernel_ms\": %.3f, \"write_s\": %.3f, \"wall_s\": %.3f}\n", t1 - t0, t2 - t1,
+               (double)kernel_ms, t3 - t2, t3 - t0);
       srt_model_destroy(m);
       return 0;
     }

@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "srt_host.hpp"
+#include "srt_xform.hpp"
 
 #include <charconv>
 #include <cerrno>
@@ -22,36 +23,9 @@ int srt_set_error(int code, const char *fmt, ...);
 namespace srt_host {
 
 // ---------------------------------------------------------------------------------------------
-// xform_double: get_q_c_d (Get_q_c.f95:4-30) -> t1_d inverse (T1.f95) -> t2_d (T2.f95) -> mu (T4.f95)
-static void rot_x(double a, const double in[3], double out[3]) {
-  double c = cos(a), s = sin(a);
-  out[0] = in[0]; out[1] = in[1] * c + in[2] * s; out[2] = in[2] * c - in[1] * s;
-}
-static void rot_z(double a, const double in[3], double out[3]) {
-  double c = cos(a), s = sin(a);
-  out[0] = in[0] * c + in[1] * s; out[1] = in[1] * c - in[0] * s; out[2] = in[2];
-}
-double dipole_tilt(int yearday, int msec) {
-  const double degrad = 3.141592653589793238462643 / 180.0;
-  int iyr = yearday / 1000, iday = yearday - iyr * 1000;
-  double ut = msec / 3600000.0, fracday = ut / 24.0;
-  double rmjd = 45.0 + (double)(iyr - 1859) * 365.0 + ((double)((iyr - 1861) / 4) + 1.0) + (double)iday - 1.0 + fracday;
-  double factor = (rmjd - 46066.0) / 365.25;
-  double phi = (78.8 + 4.283e-2 * factor) * degrad;
-  double lamda = (289.1 - 1.413e-2 * factor) * degrad;
-  double qg[3] = {cos(phi) * cos(lamda), cos(phi) * sin(lamda), sin(phi)};
-  double t0 = (rmjd - 51544.5) / 36525.0; // T0.f95
-  double theta = (100.461 + 36000.770 * t0 + 15.04107 * ut) * degrad;
-  double tmp[3], tmp2[3], qc[3];
-  rot_z(-theta, qg, tmp);
-  double eps = (23.439 - 0.013 * t0) * degrad;
-  double m = (357.528 + 35999.05 * t0 + 0.04107 * ut) * degrad;
-  double cg = 280.46 + 36000.772 * t0 + 0.04107 * ut;
-  double lamdas = (cg + (1.915 - 0.0048 * t0) * sin(m) + 0.02 * sin(2.0 * m)) * degrad;
-  rot_x(eps, tmp, tmp2);
-  rot_z(lamdas, tmp2, qc);
-  return -atan(qc[0] / sqrt(qc[1] * qc[1] + qc[2] * qc[2]));
-}
+// xform_double: get_q_c_d (Get_q_c.f95:4-30) -> t1_d inverse (T1.f95) -> t2_d (T2.f95) -> mu (T4.f95): the angles of the
+// whole chain T1 .. T5 are computed in one place, srt_xform.hpp
+double dipole_tilt(int yearday, int msec) { return srt::xform::angles(yearday, msec).mu; }
 
 // ---------------------------------------------------------------------------------------------
 // IGRF set-up for one date (host, once per model): what RECALC_08 leaves in COMMON /GEOPACK1/ and /GEOPACK2/ that
@@ -853,5 +827,61 @@ extern "C" int srt_write_ray_file(const char *path, int append, int64_t raynum0,
   for (int t = 0; t < nth; ++t)
     if (fail[t]) return srt_set_error(SRT_EIO, "%s: write failed", path);
   if (rc != 0) return srt_set_error(SRT_EIO, "%s: close failed", path);
+  return SRT_OK;
+}
+
+// ---- frame rotation SM <-> MAG (xform_double's sm_to_mag_d / mag_to_sm_d; srt_xform.hpp) ----
+extern "C" int srt_sm_to_mag(int yearday, int msec, int inverse, int64_t n, const double *x, double *out) {
+  if (inverse != 0 && inverse != 1) return srt_set_error(SRT_EINVAL, "srt_sm_to_mag: inverse = %d is neither 0 (SM -> MAG) nor 1 (MAG -> SM)", inverse);
+  if (n < 0 || (n > 0 && (!x || !out))) return srt_set_error(SRT_EINVAL, "srt_sm_to_mag: bad argument");
+  const srt::xform::Chain ch = srt::xform::chain(yearday, msec, inverse == 1);
+  for (int64_t i = 0; i < n; ++i) srt::xform::apply(ch, x + 3 * i, out + 3 * i);
+  return SRT_OK;
+}
+
+// ---- dump files: the last lines of dumpmodel.f95 (:1284-1292): (5i10) nspec nx ny nz; (6es24.15e3) the bounds; then every
+// value of f(4 nspec + 3, nx, ny, nz) in array order, one (es24.15e3) record each
+extern "C" int srt_dump_file_write(const char *path, int nspec, int nx, int ny, int nz, const double bounds[6], const double *f) {
+  if (!path || !bounds || !f) return srt_set_error(SRT_EINVAL, "null argument");
+  if (nspec < 1 || nspec > SRT_MAXSPEC || nx < 1 || ny < 1 || nz < 1) return srt_set_error(SRT_EINVAL, "bad dump shape");
+  const size_t n = (size_t)nx * ny * nz * (4 * (size_t)nspec + 3);
+  FILE *fp = fopen(path, "w");
+  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
+  std::vector<char> big(1 << 22);
+  setvbuf(fp, big.data(), _IOFBF, big.size());
+  char num[25];
+  fprintf(fp, "%10d%10d%10d%10d\n", nspec, nx, ny, nz);
+  for (int k = 0; k < 6; ++k) { srt_host::format_es24(bounds[k], num); fputs(num, fp); }
+  fputc('\n', fp);
+  for (size_t c = 0; c < n; ++c) {
+    srt_host::format_es24(f[c], num);
+    num[24] = '\n';
+    fwrite(num, 1, 25, fp);
+  }
+  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
+  return SRT_OK;
+}
+
+extern "C" int srt_dump_file_read(const char *path, int32_t dims[4], double bounds[6], double **f) {
+  if (!path || !dims || !bounds || !f) return srt_set_error(SRT_EINVAL, "null argument");
+  *f = nullptr;
+  std::vector<double> all;
+  std::string err;
+  if (!srt_host::read_all_numbers(path, all, err)) return srt_set_error(SRT_EIO, "%s: %s", path, err.c_str());
+  if (all.size() < 10) return srt_set_error(SRT_EIO, "%s: dump file header incomplete", path);
+  for (int k = 0; k < 4; ++k) {
+    if (!(all[k] >= 1.0 && all[k] <= 2147483647.0) || all[k] != std::floor(all[k]) || (k == 0 && all[k] > SRT_MAXSPEC))
+      return srt_set_error(SRT_EIO, "%s: dump file header: %s = %g", path, k == 0 ? "nspec" : k == 1 ? "nx" : k == 2 ? "ny" : "nz", all[k]);
+    dims[k] = (int32_t)all[k];
+  }
+  const double want = (4.0 * dims[0] + 3.0) * dims[1] * dims[2] * dims[3];
+  if ((double)(all.size() - 10) != want)
+    return srt_set_error(SRT_EIO, "%s: dump file holds %zu values, its header (nspec nx ny nz = %d %d %d %d) announces %.0f", path,
+                         all.size() - 10, dims[0], dims[1], dims[2], dims[3], want);
+  for (int k = 0; k < 6; ++k) bounds[k] = all[4 + k];
+  const size_t n = all.size() - 10;
+  *f = (double *)malloc(n * sizeof(double));
+  if (!*f) return srt_set_error(SRT_ENOMEM, "dump of %zu values", n);
+  memcpy(*f, all.data() + 10, n * sizeof(double));
   return SRT_OK;
 }

@@ -208,6 +208,36 @@ module srt_bindc
        real(c_double) :: qs(*), ms(*), w0(*), rows(*)
        integer(c_int32_t) :: nrows(*), stopcond(*)
      end function srt_write_ray_file
+     ! dumpmodel.f95: f(4*nspec+3, nx, ny, nz) = (/qs, Ns, ms, nus, B0/) of every node; mag_coords = 1: the grid is in MAG
+     integer(c_int) function srt_dump_model(model, nx, ny, nz, bounds, mag_coords, f) bind(C, name="srt_dump_model")
+       import :: c_int, c_ptr, c_double
+       type(c_ptr), value :: model
+       integer(c_int), value :: nx, ny, nz, mag_coords
+       real(c_double), intent(in) :: bounds(6)   ! minx maxx miny maxy minz maxz
+       real(c_double) :: f(*)
+     end function srt_dump_model
+     ! xform_double's sm_to_mag_d (inverse = 0) / mag_to_sm_d (inverse = 1) for x(3,n); itime = (yearday, msec)
+     integer(c_int) function srt_sm_to_mag(yearday, msec, inverse, n, x, out) bind(C, name="srt_sm_to_mag")
+       import :: c_int, c_int64_t, c_double
+       integer(c_int), value :: yearday, msec, inverse
+       integer(c_int64_t), value :: n
+       real(c_double), intent(in) :: x(3,*)
+       real(c_double) :: out(3,*)
+     end function srt_sm_to_mag
+     ! the text file dumpmodel.f95 writes; the reader's f is a c_ptr to malloc'd doubles (srt_free)
+     integer(c_int) function srt_dump_file_write(path, nspec, nx, ny, nz, bounds, f) bind(C, name="srt_dump_file_write")
+       import :: c_int, c_char, c_double
+       character(kind=c_char), dimension(*) :: path
+       integer(c_int), value :: nspec, nx, ny, nz
+       real(c_double), intent(in) :: bounds(6), f(*)
+     end function srt_dump_file_write
+     integer(c_int) function srt_dump_file_read(path, dims, bounds, f) bind(C, name="srt_dump_file_read")
+       import :: c_int, c_int32_t, c_char, c_double, c_ptr
+       character(kind=c_char), dimension(*) :: path
+       integer(c_int32_t) :: dims(4)   ! nspec nx ny nz
+       real(c_double) :: bounds(6)
+       type(c_ptr) :: f
+     end function srt_dump_file_read
      subroutine srt_free(ptr) bind(C, name="srt_free")
        import :: c_ptr
        type(c_ptr), value :: ptr
