@@ -322,6 +322,72 @@ int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t nrays, con
 int srt_pack_rows_device(int32_t slots, int32_t outputper, int64_t nrays, const double *d_rows,
                          const int32_t *d_nrows, int64_t *d_offsets, double *d_packed, int64_t capacity_rows,
                          void *stream);
+/* ---- the hot path in segments: bounded row memory, pause and resume ----
+ * A launch of srt_trace_batch_device needs rows[nrays][slots][SRT_ROW] up front, whatever the rays turn out to need.  A
+ * SEGMENTED trace runs the same rays as a sequence of launches.  With N = segment_rows and S = N * outputper, segment
+ * s = 0, 1, .. owns the row indices [s S, (s + 1) S): a kept row r of that range goes to slot r / outputper - s N of a row
+ * buffer [nrays][N][SRT_ROW].  A ray that has not stopped when it reaches the end of the range is PAUSED at the loop top,
+ * behind the reference's own tests (t >= tmax, then the stop conditions: a ray at maxsteps stops with SRT_STOP_MAXSTEPS and is
+ * never paused): nrows = (s + 1) S, stopcond = SRT_RUNNING, and its integrator state goes to its record of SRT_STATE doubles:
+ *     [0..5] pos, k   [6..11] the right-hand side there (the carried first RK stage)   [12..14] vgrel   [15] t   [16] dt
+ * The step counter travels in nrows; a ray can pause only right after an accepted step (or its launch), where the
+ * controller's two flags are determined: no refinement pending, and "first attempt" exactly when nrows == 1.  The next
+ * segment restores the record and the ray goes on as if it had never left its lane: the rows of a segmented trace, nrows and
+ * stopcond are those of srt_trace_batch_device BIT FOR BIT, for every N and every model but one.
+ * DEFINED BEHAVIOUR for modelnum 4 (scattered samples): a lane's block of candidate samples is forgotten when the lane takes a
+ * ray, and the block's contents fix the order of the model's sums.  Segment 0 is bit-equal to the unsegmented launch; rows
+ * behind the first pause agree to the rounding of a reordered sum, grown by the trajectory's own sensitivity.  nrows and
+ * stopcond agree.  (Rebuilding the block about a saved centre would remove this; it is not done.) */
+#define SRT_RUNNING (-1) /* stopcond of a paused ray */
+#define SRT_STATE 17     /* doubles in a paused ray's record */
+/* segments a segmented trace has at most = ceil(srt_rows_per_ray(p) / segment_rows); 0 for bad arguments.  Pure host code. */
+int32_t srt_trace_segments(const srt_params *p, int32_t segment_rows);
+/* One segment, beside srt_trace_batch_device (same inputs, same d_counters, same asynchrony).
+ *   d_queue  segment 0: NULL, every ray is launched (ray_order applies here only).  Later segments: nqueue ray ids (int32),
+ *            the rays to resume -- what srt_running_rays_device returned after the previous segment.  nqueue = 0 launches nothing.
+ *   d_state[nrays][SRT_STATE], d_nrows[nrays], d_stopcond[nrays] persist from segment to segment; the entries of rays that
+ *            are not in the queue are not touched.
+ *   d_rows[nrays][segment_rows][SRT_ROW] receives this segment's kept rows (a ray's slot 0 is kept row segment * segment_rows).
+ *   d_counters[1] = steps accepted in THIS launch; over all segments they sum to the unsegmented figure.
+ * SRT_EINVAL, by name, before the device is touched: segment_rows < 1; segment_rows > srt_rows_per_ray(p); nrays >= 2^31;
+ * segment < 0; a later segment without a queue; a queue in segment 0.  (After srt_trace_segments(p, segment_rows) segments
+ * no ray is left running: every ray has stopped at maxsteps at the latest.) */
+int srt_trace_segment_device(srt_model *m, const srt_params *p, int64_t nrays, const double *d_pos0, const double *d_dir0,
+                             const double *d_w0, int32_t segment_rows, int32_t segment, const int32_t *d_queue,
+                             int64_t nqueue, double *d_state, double *d_rows, int32_t *d_nrows, int32_t *d_stopcond,
+                             int64_t *d_counters, void *stream);
+/* d_queue[0 .. *d_count) = the ids of the rays with stopcond == SRT_RUNNING, ascending (a stable compaction); d_queue has room
+ * for nrays ids, d_count is one int32 on the device.  The device is found from the buffers, as in srt_pack_rows_device.
+ * Asynchronous on `stream`. */
+int srt_running_rays_device(int64_t nrays, const int32_t *d_stopcond, int32_t *d_queue, int32_t *d_count, void *stream);
+/* The host iterator over the segments of one launch set: device memory nrays * segment_rows rows (twice: traced and packed)
+ * instead of nrays * slots, and only rows that exist reach the host.
+ *   srt_trace_run_open   uploads the launch set (pos0 / dir0 [nrays][3], w0 [nrays], host) and allocates; no launch yet.
+ *   srt_trace_run_next   runs the next segment; returns 1 and fills *seg, 0 when the run is over (no ray left running, or
+ *                        srt_trace_segments(p, segment_rows) segments done -- the bound of every loop over it), < 0 on error.
+ *   srt_trace_run_close  frees everything (NULL is allowed).
+ * *seg is valid until the next call on the same run:
+ *   nrays               rays that ran in this segment (all of them in segment 0)
+ *   ray[nrays]          their ids, ascending
+ *   offsets[nrays + 1]  exclusive prefix sums of their kept-row counts IN THIS SEGMENT
+ *   rows[offsets[nrays]][SRT_ROW]  those rows, ray after ray: ray[i]'s kept rows number segment * segment_rows onwards
+ *   nrows[nrays], stopcond[nrays]  each ray's rows so far and SRT_RUNNING or its stop code
+ *   accepted_steps      steps accepted in this segment */
+typedef struct srt_trace_run srt_trace_run;
+typedef struct srt_segment {
+  int32_t segment, reserved;
+  int64_t nrays;
+  const int32_t *ray;
+  const int64_t *offsets;
+  const double *rows;
+  const int32_t *nrows;
+  const int32_t *stopcond;
+  int64_t accepted_steps;
+} srt_segment;
+int srt_trace_run_open(srt_model *m, const srt_params *p, int64_t nrays, const double *pos0, const double *dir0,
+                       const double *w0, int32_t segment_rows, srt_trace_run **run);
+int srt_trace_run_next(srt_trace_run *run, srt_segment *seg);
+void srt_trace_run_close(srt_trace_run *run);
 /* duration in ms of the most recent trace kernel on this model (or of the launches of the most recent srt_dump_model), measured
  * with HIP events on the stream it ran on (synchronises that stream) */
 int srt_last_kernel_ms(srt_model *m, float *ms);
@@ -367,6 +433,12 @@ int srt_write_ray_file(const char *path, int append, int64_t raynum0, int64_t nr
                        const srt_params *p, int nspec, const double *qs, const double *ms,
                        const double *w0, const double *rows, const int32_t *nrows,
                        const int32_t *stopcond);
+/* The same file from the packed layout srt_read_ray_file returns and a segmented trace delivers: rows[offsets[nrays]][SRT_ROW]
+ * = the kept rows of ray 0, ray 1, .. back to back, offsets[nrays + 1] their exclusive prefix sums (offsets[0] = 0).  One
+ * formatting routine serves both writers: equal rows give equal bytes.  Pure host code, needs no GPU. */
+int srt_write_ray_file_packed(const char *path, int append, int64_t raynum0, int64_t nrays, int nspec, const double *qs,
+                              const double *ms, const double *w0, const int64_t *offsets, const double *rows,
+                              const int32_t *stopcond);
 /* .ray reader: the inverse of srt_write_ray_file, for files written by this library or by the reference's driver (what
  * matlab/readrayoutput.m is to the MATLAB damping scripts): returns the number of rays (< 0: error) and malloc'd arrays
  * (srt_free): raynum / stopcond / kept (records of the ray) / w0 per ray, rows[nrecords][SRT_ROW] = the kept rows of all rays

@@ -54,6 +54,17 @@ class DampingParams(C.Structure):
                 ("Ne_h", C.c_double), ("kT", C.c_double), ("tol", C.c_double)]
 
 
+class Segment(C.Structure):
+    """srt_segment of include/srt.h: what one call of srt_trace_run_next hands out."""
+    _fields_ = [("segment", C.c_int32), ("reserved", C.c_int32), ("nrays", C.c_int64), ("ray", ip),
+                ("offsets", C.POINTER(C.c_int64)), ("rows", dp), ("nrows", ip), ("stopcond", ip),
+                ("accepted_steps", C.c_int64)]
+
+
+RUNNING = -1  # SRT_RUNNING: stopcond of a paused ray
+STATE = 17    # SRT_STATE: doubles in a paused ray's record
+
+
 def library_path():
     return _build.LIB
 
@@ -115,6 +126,17 @@ def lib():
     L.srt_trace_batch.argtypes = [vp, C.POINTER(Params), C.c_int64, dp, dp, dp, dp, ip, ip, C.POINTER(C.c_int64)]
     L.srt_trace_batch_device.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.srt_pack_rows_device.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int64, vp]
+    L.srt_trace_segments.argtypes = [C.POINTER(Params), C.c_int32]
+    L.srt_trace_segments.restype = C.c_int32
+    L.srt_trace_segment_device.argtypes = [vp, C.POINTER(Params), C.c_int64, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int64,
+                                           vp, vp, vp, vp, vp, vp]
+    L.srt_running_rays_device.argtypes = [C.c_int64, vp, vp, vp, vp]
+    L.srt_trace_run_open.argtypes = [vp, C.POINTER(Params), C.c_int64, dp, dp, dp, C.c_int32, C.POINTER(vp)]
+    L.srt_trace_run_next.argtypes = [vp, C.POINTER(Segment)]
+    L.srt_trace_run_close.argtypes = [vp]
+    L.srt_trace_run_close.restype = None
+    L.srt_write_ray_file_packed.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.c_int, dp, dp, dp,
+                                            C.POINTER(C.c_int64), dp, ip]
     L.srt_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_launch_ms.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
     L.srt_read_rays_file.argtypes = [C.c_char_p, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]
@@ -440,6 +462,46 @@ class Model:
                                      nrows.ctypes.data_as(ip), stop.ctypes.data_as(ip), C.byref(steps)))
         return rows, nrows, stop, steps.value
 
+    def trace_segments(self, pos0, dir0, w0, segment_rows, params=None, **kw):
+        """The same rays traced in segments of `segment_rows` kept rows per ray and launch: device memory for
+        n * segment_rows rows instead of n * slots, and only rows that exist come back.  A generator; each item is a dict
+        of one segment: segment (its number), ray[m] (ids of the rays that ran, ascending), offsets[m+1] and
+        rows[offsets[m], 20] (their kept rows of this segment, ray after ray), nrows[m] (rows so far), stopcond[m]
+        (RUNNING = -1 for a paused ray), steps (accepted in this segment), kernel_ms.  Every model but the scattered one
+        gives the rows of `trace` bit for bit (include/srt.h)."""
+        p = params if params is not None else make_params(**kw)
+        pos0, dir0, w0 = _f64(pos0, (-1, 3)), _f64(dir0, (-1, 3)), _f64(w0, (-1,))
+        run = C.c_void_p()
+        _check(lib().srt_trace_run_open(self.h, C.byref(p), pos0.shape[0], _dp(pos0), _dp(dir0), _dp(w0), int(segment_rows),
+                                        C.byref(run)))
+        try:
+            seg = Segment()
+            for _ in range(trace_segment_count(p, segment_rows)):  # the bound; the run ends sooner when no ray is left
+                rc = lib().srt_trace_run_next(run, C.byref(seg))
+                if rc < 0:
+                    _check(rc)
+                if rc == 0:
+                    break
+                m = seg.nrays
+                off = np.ctypeslib.as_array(seg.offsets, (m + 1,)).copy()
+                total = int(off[m])
+                yield {"segment": seg.segment,
+                       "ray": np.ctypeslib.as_array(seg.ray, (m,)).copy(),
+                       "offsets": off,
+                       "rows": np.ctypeslib.as_array(seg.rows, (total, ROW)).copy() if total else np.zeros((0, ROW)),
+                       "nrows": np.ctypeslib.as_array(seg.nrows, (m,)).copy(),
+                       "stopcond": np.ctypeslib.as_array(seg.stopcond, (m,)).copy(),
+                       "steps": seg.accepted_steps, "kernel_ms": self.last_kernel_ms()}
+        finally:
+            lib().srt_trace_run_close(run)
+
+    def trace_packed(self, pos0, dir0, w0, segment_rows, params=None, **kw):
+        """`trace` through trace_segments, whole trajectories in the packed layout: offsets[n+1], rows[offsets[n], 20] = the
+        kept rows of ray 0, ray 1, .. back to back (what read_ray_file returns and write_ray_file_packed takes), nrows[n],
+        stopcond[n], accepted_steps."""
+        n = _f64(pos0, (-1, 3)).shape[0]
+        return assemble_segments(n, self.trace_segments(pos0, dir0, w0, segment_rows, params=params, **kw))
+
     def launch_ms(self, back=0):
         ms = C.c_float()
         _check(lib().srt_launch_ms(self.h, back, C.byref(ms)))
@@ -511,6 +573,59 @@ def write_ray_file(path, species, params, w0, rows, nrows, stopcond, raynum0=1, 
     _check(lib().srt_write_ray_file(os.fsencode(path), int(append), raynum0, w0.shape[0], C.byref(params), nspec,
                                     _dp(qs), _dp(ms), _dp(w0), _dp(rows), nrows.ctypes.data_as(ip),
                                     stopcond.ctypes.data_as(ip)))
+
+
+def assemble_segments(n, segments):
+    """The items of Model.trace_segments for n rays -> offsets[n+1], rows[offsets[n], 20] (whole trajectories, ray-major),
+    nrows[n], stopcond[n], accepted_steps."""
+    nrows, stop = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    kept = np.zeros(n, dtype=np.int64)
+    segs, steps = [], 0
+    for sg in segments:
+        ids = sg["ray"]
+        nrows[ids], stop[ids] = sg["nrows"], sg["stopcond"]
+        kept[ids] += np.diff(sg["offsets"])
+        steps += sg["steps"]
+        segs.append(sg)
+    offsets = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+    rows = np.zeros((int(offsets[n]), ROW))
+    fill = offsets[:-1].copy()  # where each ray's next rows go
+    for sg in segs:
+        cnt = np.diff(sg["offsets"])
+        if cnt.sum() == 0:
+            continue
+        # row j of the segment belongs to ray[i] with offsets[i] <= j < offsets[i+1]
+        owner = np.repeat(np.arange(len(cnt)), cnt)
+        rows[fill[sg["ray"]][owner] + (np.arange(cnt.sum()) - sg["offsets"][:-1][owner])] = sg["rows"]
+        fill[sg["ray"]] += cnt
+    return offsets, rows, nrows, stop, steps
+
+
+def trace_segment_count(params, segment_rows):
+    """srt_trace_segments: segments a segmented trace has at most = ceil(slots / segment_rows); needs no GPU."""
+    return lib().srt_trace_segments(C.byref(params), int(segment_rows))
+
+
+def write_ray_file_packed(path, species, w0, offsets, rows, stopcond, raynum0=1, append=False):
+    """write_ray_file from the packed layout (read_ray_file, Model.trace_packed): offsets[n+1], rows[offsets[n], 20].
+    species: a Model, or (nspec, qs, ms).  Equal rows give the bytes write_ray_file gives."""
+    if isinstance(species, Model):
+        qs, ms = species.species()
+        nspec = species.nspec
+    else:
+        nspec, qs, ms = species
+        qs, ms = _f64(qs), _f64(ms)
+    w0 = _f64(w0, (-1,))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets.shape != (w0.shape[0] + 1,):
+        raise ValueError("offsets has %d entries for %d rays" % (offsets.size, w0.shape[0]))
+    rows = _f64(rows).reshape(-1, ROW)
+    if rows.shape[0] < (offsets[-1] if offsets.size else 0):
+        raise ValueError("offsets name %d rows, rows holds %d" % (offsets[-1], rows.shape[0]))
+    stopcond = np.ascontiguousarray(stopcond, dtype=np.int32)
+    _check(lib().srt_write_ray_file_packed(os.fsencode(path), int(append), raynum0, w0.shape[0], nspec, _dp(qs), _dp(ms),
+                                           _dp(w0), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(rows),
+                                           stopcond.ctypes.data_as(ip)))
 
 
 def read_ray_file(path):

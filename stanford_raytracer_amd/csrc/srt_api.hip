@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -1701,17 +1702,24 @@ static int slot_scratch(srt_model *m, srt_model::LaunchSlot &sl, srt_model::Scra
   return SRT_OK;
 }
 
-extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t nrays, const double *d_pos0,
-                                      const double *d_dir0, const double *d_w0, double *d_rows, int32_t *d_nrows,
-                                      int32_t *d_stopcond, int64_t *d_counters, void *stream) {
-  if (!m || !d_pos0 || !d_dir0 || !d_w0 || !d_rows || !d_nrows || !d_stopcond || !d_counters || nrays < 0)
-    return srt_set_error(SRT_EINVAL, "bad argument");
-  int rc = check_params(p);
-  if (rc) return rc;
+// one segment of a segmented trace (srt_trace_segment_device); nullptr = the unsegmented launch
+struct SegLaunch {
+  int32_t rows, segment;
+  const int32_t *queue;
+  int64_t nqueue;
+  double *state;
+};
+static_assert(SRT_STATE == TRACE_STATE, "srt.h and srt_kernels.hpp disagree on a paused ray's record");
+
+// the one launch path of the trace kernels: arguments checked by the two entry points below
+static int trace_launch(srt_model *m, const srt_params *p, int64_t nrays, const double *d_pos0, const double *d_dir0,
+                        const double *d_w0, double *d_rows, int32_t *d_nrows, int32_t *d_stopcond, int64_t *d_counters,
+                        void *stream, const SegLaunch *sg) {
+  int rc;
   SRT_MODEL_SCOPE;
   if ((rc = ensure_model(m))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  TraceArgs a;
+  TraceSegArgs a; // (the unsegmented kernels take its TraceArgs part)
   a.pos0 = d_pos0;
   a.dir0 = d_dir0;
   a.w0 = d_w0;
@@ -1727,8 +1735,14 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   a.p.first_attempt_policy = p->first_attempt_policy;
   a.p.refill_threshold = p->refill_threshold;
   a.p.slots = srt_rows_per_ray(p);
-  a.order = nullptr;
+  a.order = sg ? sg->queue : nullptr;
+  a.state = sg ? sg->state : nullptr;
+  a.nqueue = sg && sg->segment > 0 ? sg->nqueue : nrays;
+  a.seg_rows = sg ? sg->rows : 0;
+  a.segment = sg ? sg->segment : 0;
+  const long long nwork = a.nqueue; // rays this launch works on
   HIP_OK(hipMemsetAsync(d_counters, 0, 4 * sizeof(int64_t), st));
+  if (nwork == 0 && sg) return SRT_OK;
   // persistent grid: enough one-wave blocks to fill the chip, never more than the rays need
   int per_cu = 0;
   rc = with_model(m, [&](auto tag) -> int {
@@ -1751,7 +1765,7 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
     if (v >= 1 && v <= WAVE) cap = v;
   }
   a.p.wave_cap = cap;
-  long long want = (nrays + cap - 1) / cap;
+  long long want = (nwork + cap - 1) / cap;
   if (grid > want) grid = want;
   if (grid < 1) grid = 1;
   // scratch slot: one whose last launch is over (preferring one that holds buffers already), else a fresh one, else -- all
@@ -1775,7 +1789,7 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   srt_model::LaunchTimes &lt = m->hist[m->next_hist];
   HIP_OK(hipEventRecord(lt.ev0, st));
   const InterpModel &im = m->as<InterpModel>();
-  if (p->ray_order >= 1 && (m->kind == KIND_INTERP || m->kind == KIND_INTERP_NODES) && nrays > WAVE && nrays < (1ll << 31) && im.ax.n < 1023 && im.ay.n < 1023 &&
+  if (p->ray_order >= 1 && a.segment == 0 && (m->kind == KIND_INTERP || m->kind == KIND_INTERP_NODES) && nrays > WAVE && nrays < (1ll << 31) && im.ax.n < 1023 && im.ay.n < 1023 &&
       im.az.n < 1023) {
     // work through the launch set in the order of the rays' launch cells (inside the timed region)
     if ((size_t)nrays > sl.ids[1].cap) {
@@ -1823,15 +1837,20 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVE), 0, st, m->on_device<M>(), m->d_common.p, a);
     };
-    if (fixed) {
-      if (fopt == 2) launch(trace_kernel<M, true, T::lds, 2>);
-      else if (fopt == 1) launch(trace_kernel<M, true, T::lds, 1>);
-      else launch(trace_kernel<M, true, T::lds, 0>);
-    } else {
-      if (fopt == 2) launch(trace_kernel<M, false, T::lds, 2>);
-      else if (fopt == 1) launch(trace_kernel<M, false, T::lds, 1>);
-      else launch(trace_kernel<M, false, T::lds, 0>);
-    }
+    auto pick = [&](auto seg) { // (its segmented twin beside every kernel)
+      constexpr bool SEG = decltype(seg)::value;
+      if (fixed) {
+        if (fopt == 2) launch(trace_kernel<M, true, T::lds, 2, SEG>);
+        else if (fopt == 1) launch(trace_kernel<M, true, T::lds, 1, SEG>);
+        else launch(trace_kernel<M, true, T::lds, 0, SEG>);
+      } else {
+        if (fopt == 2) launch(trace_kernel<M, false, T::lds, 2, SEG>);
+        else if (fopt == 1) launch(trace_kernel<M, false, T::lds, 1, SEG>);
+        else launch(trace_kernel<M, false, T::lds, 0, SEG>);
+      }
+    };
+    if (sg) pick(std::true_type{});
+    else pick(std::false_type{});
     return SRT_OK;
   });
   if (rc) return rc;
@@ -1884,6 +1903,83 @@ extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t
   lt.used = true;
   m->last_hist = m->next_hist;
   m->next_hist = (m->next_hist + 1) % srt_model::NHIST;
+  return SRT_OK;
+}
+
+extern "C" int srt_trace_batch_device(srt_model *m, const srt_params *p, int64_t nrays, const double *d_pos0,
+                                      const double *d_dir0, const double *d_w0, double *d_rows, int32_t *d_nrows,
+                                      int32_t *d_stopcond, int64_t *d_counters, void *stream) {
+  if (!m || !d_pos0 || !d_dir0 || !d_w0 || !d_rows || !d_nrows || !d_stopcond || !d_counters || nrays < 0)
+    return srt_set_error(SRT_EINVAL, "bad argument");
+  int rc = check_params(p);
+  if (rc) return rc;
+  return trace_launch(m, p, nrays, d_pos0, d_dir0, d_w0, d_rows, d_nrows, d_stopcond, d_counters, stream, nullptr);
+}
+
+// ---- the hot path in segments (srt.h): pure host code first
+extern "C" int32_t srt_trace_segments(const srt_params *p, int32_t segment_rows) {
+  const int32_t slots = srt_rows_per_ray(p);
+  if (slots < 1 || segment_rows < 1) return 0;
+  return (int32_t)(((int64_t)slots + segment_rows - 1) / segment_rows);
+}
+// the refusals every segmented entry point shares, by name, before the device is touched
+static int check_segments(const srt_params *p, int64_t nrays, int32_t segment_rows) {
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (segment_rows < 1) return srt_set_error(SRT_EINVAL, "segment_rows=%d: a segment keeps at least one row per ray", (int)segment_rows);
+  if (segment_rows > srt_rows_per_ray(p))
+    return srt_set_error(SRT_EINVAL, "segment_rows=%d exceeds the %d rows a ray keeps at most (srt_rows_per_ray)", (int)segment_rows,
+                         (int)srt_rows_per_ray(p));
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "nrays=%lld is negative", (long long)nrays);
+  if (nrays >= (1ll << 31)) return srt_set_error(SRT_EINVAL, "nrays=%lld: a segmented trace takes fewer than 2^31 rays (ray ids are int32)", (long long)nrays);
+  return SRT_OK;
+}
+
+extern "C" int srt_trace_segment_device(srt_model *m, const srt_params *p, int64_t nrays, const double *d_pos0, const double *d_dir0,
+                                        const double *d_w0, int32_t segment_rows, int32_t segment, const int32_t *d_queue,
+                                        int64_t nqueue, double *d_state, double *d_rows, int32_t *d_nrows, int32_t *d_stopcond,
+                                        int64_t *d_counters, void *stream) {
+  int rc = check_segments(p, nrays, segment_rows);
+  if (rc) return rc;
+  if (segment < 0) return srt_set_error(SRT_EINVAL, "segment=%d is negative", (int)segment);
+  if (segment > 0 && !d_queue) return srt_set_error(SRT_EINVAL, "segment %d without a queue: later segments resume the rays d_queue names", (int)segment);
+  if (segment == 0 && d_queue) return srt_set_error(SRT_EINVAL, "segment 0 launches every ray: d_queue must be NULL");
+  if (segment > 0 && (nqueue < 0 || nqueue > nrays)) return srt_set_error(SRT_EINVAL, "nqueue=%lld is not within 0 .. nrays", (long long)nqueue);
+  if (!m || !d_pos0 || !d_dir0 || !d_w0 || !d_state || !d_rows || !d_nrows || !d_stopcond || !d_counters)
+    return srt_set_error(SRT_EINVAL, "null argument");
+  const SegLaunch sg = {segment_rows, segment, d_queue, nqueue, d_state};
+  return trace_launch(m, p, nrays, d_pos0, d_dir0, d_w0, d_rows, d_nrows, d_stopcond, d_counters, stream, &sg);
+}
+
+struct IsRunning {
+  __host__ __device__ int operator()(int32_t stop) const { return stop == SRT_RUNNING ? 1 : 0; }
+};
+extern "C" int srt_running_rays_device(int64_t nrays, const int32_t *d_stopcond, int32_t *d_queue, int32_t *d_count, void *stream) {
+  if (nrays < 0 || !d_count || (nrays > 0 && (!d_stopcond || !d_queue))) return srt_set_error(SRT_EINVAL, "bad argument");
+  if (nrays >= (1ll << 31)) return srt_set_error(SRT_EINVAL, "nrays=%lld: ray ids are int32", (long long)nrays);
+  int dev = -1, rc;
+  {
+    const void *ptrs[3] = {d_count, nrays > 0 ? (const void *)d_stopcond : nullptr, nrays > 0 ? (const void *)d_queue : nullptr};
+    if ((rc = device_of("srt_running_rays_device", ptrs, 3, &dev))) return rc;
+  }
+  DeviceScope scope;
+  if ((rc = scope.enter(dev))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (nrays == 0) {
+    HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int32_t), st));
+    return SRT_OK;
+  }
+  // ids 0 .. nrays - 1 selected by their flag; DeviceSelect keeps the input's order, so the queue is ascending
+  hipcub::CountingInputIterator<int32_t> ids(0);
+  auto flags = hipcub::TransformInputIterator<int, IsRunning, const int32_t *>(d_stopcond, IsRunning{});
+  size_t need = 0;
+  HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, need, ids, flags, d_queue, d_count, (int)nrays, st));
+  void *tmp = nullptr;
+  HIP_OK(hipMallocAsync(&tmp, need ? need : 16, st));
+  const hipError_t e = hipcub::DeviceSelect::Flagged(tmp, need, ids, flags, d_queue, d_count, (int)nrays, st);
+  const hipError_t ef = hipFreeAsync(tmp, st); // (also on the error path)
+  HIP_OK(e);
+  HIP_OK(ef);
   return SRT_OK;
 }
 
@@ -2116,4 +2212,158 @@ extern "C" int srt_trace_batch(srt_model *m, const srt_params *p, int64_t nrays,
     else if (accepted_steps) *accepted_steps = c[1];
   }
   return rc;
+}
+
+// ---- the host iterator over the segments of one launch set (srt.h) ----
+// this segment's kept rows of every ray, in the form srt_pack_rows_device counts them: a "row count" whose kept rows are the
+// ray's kept rows with index in [segment N, (segment + 1) N) -- none for a ray that stopped in an earlier segment
+__global__ void segment_rows_kernel(long long nrays, const int32_t *__restrict__ nrows, int outputper, int slots, int N, int segment,
+                                    int32_t *__restrict__ segn) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nrays) return;
+  const int32_t n = nrows[i];
+  long long k = n > 0 ? (n - 1) / outputper + 1 : 0;
+  if (k > slots) k = slots;
+  k -= (long long)segment * N;
+  if (k > N) k = N;
+  segn[i] = k > 0 ? (int32_t)((k - 1) * outputper + 1) : 0;
+}
+
+struct srt_trace_run {
+  srt_model *m = nullptr;
+  int device = 0;
+  srt_params p{};
+  int64_t nrays = 0, nq = 0; // nq: rays the next segment works on
+  int32_t N = 0, nseg = 0, seg = 0;
+  DevBuf<double> pos, dir, w, state, rows, packed;
+  DevBuf<int32_t> nrows, stop, queue, segn, count;
+  DevBuf<int64_t> offsets, counters;
+  // host side: the next segment's queue, and what *seg of the last srt_trace_run_next points into
+  std::vector<int32_t> hq, ray, h_nrows, h_stop, all_nrows, all_stop;
+  std::vector<int64_t> h_off, all_off;
+  std::vector<double> h_rows;
+};
+
+extern "C" int srt_trace_run_open(srt_model *m, const srt_params *p, int64_t nrays, const double *pos0, const double *dir0,
+                                  const double *w0, int32_t segment_rows, srt_trace_run **run) {
+  int rc = check_segments(p, nrays, segment_rows);
+  if (rc) return rc;
+  if (!run) return srt_set_error(SRT_EINVAL, "null argument");
+  *run = nullptr;
+  {
+    DeviceScope probe; // without a GPU there is nothing to trace with, and the call says so before it looks at the model
+    if ((rc = probe.enter_default())) return rc;
+  }
+  if (!m) return srt_set_error(SRT_EINVAL, "null model");
+  if (nrays > 0 && (!pos0 || !dir0 || !w0)) return srt_set_error(SRT_EINVAL, "null argument");
+  SRT_MODEL_SCOPE;
+  if ((rc = ensure_model(m))) return rc;
+  std::unique_ptr<srt_trace_run> r(new srt_trace_run);
+  r->m = m;
+  r->device = m->device;
+  r->p = *p;
+  r->nrays = r->nq = nrays;
+  r->N = segment_rows;
+  r->nseg = srt_trace_segments(p, segment_rows);
+  if (nrays > 0) {
+    const size_t n = (size_t)nrays, nrow = n * (size_t)segment_rows * SRT_ROW;
+    DevBuf<double> aos;
+    hipError_t e = aos.alloc(3 * n);
+    if (e == hipSuccess) e = r->pos.alloc(3 * n);
+    if (e == hipSuccess) e = r->dir.alloc(3 * n);
+    if (e == hipSuccess) e = r->w.alloc(n);
+    if (e == hipSuccess) e = r->state.alloc(n * SRT_STATE);
+    if (e == hipSuccess) e = r->rows.alloc(nrow);
+    if (e == hipSuccess) e = r->packed.alloc(nrow);
+    if (e == hipSuccess) e = r->nrows.alloc(n);
+    if (e == hipSuccess) e = r->stop.alloc(n);
+    if (e == hipSuccess) e = r->queue.alloc(n);
+    if (e == hipSuccess) e = r->segn.alloc(n);
+    if (e == hipSuccess) e = r->count.alloc(1);
+    if (e == hipSuccess) e = r->offsets.alloc(n + 1);
+    if (e == hipSuccess) e = r->counters.alloc(4);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return srt_set_error(SRT_ENOMEM, "segmented trace of %lld rays, %d rows per segment: %s", (long long)nrays, (int)segment_rows,
+                           hipGetErrorString(e));
+    }
+    const unsigned blocks = (unsigned)((nrays + 255) / 256);
+    HIP_OK(hipMemcpy(aos.p, pos0, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(aos_to_soa3, dim3(blocks), dim3(256), 0, 0, (const double *)aos.p, r->pos.p, (long long)nrays);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(aos.p, dir0, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(aos_to_soa3, dim3(blocks), dim3(256), 0, 0, (const double *)aos.p, r->dir.p, (long long)nrays);
+    HIP_OK(hipMemcpy(r->w.p, w0, n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_OK(hipDeviceSynchronize());
+  }
+  *run = r.release();
+  return SRT_OK;
+}
+
+extern "C" int srt_trace_run_next(srt_trace_run *r, srt_segment *seg) {
+  if (!r || !seg) return srt_set_error(SRT_EINVAL, "null argument");
+  memset(seg, 0, sizeof *seg);
+  if (r->seg >= r->nseg || r->nq == 0) return 0; // the bound of the loop, and a segment with no rays
+  DeviceScope scope;
+  int rc = scope.enter(r->device);
+  if (rc) return rc;
+  const int64_t n = r->nrays, nq = r->nq;
+  const int32_t s = r->seg, per = r->p.outputper < 1 ? 1 : r->p.outputper;
+  if ((rc = srt_trace_segment_device(r->m, &r->p, n, r->pos.p, r->dir.p, r->w.p, r->N, s, s > 0 ? r->queue.p : nullptr, nq, r->state.p,
+                                     r->rows.p, r->nrows.p, r->stop.p, r->counters.p, nullptr)))
+    return rc;
+  hipLaunchKernelGGL(segment_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (long long)n, (const int32_t *)r->nrows.p, (int)per,
+                     (int)srt_rows_per_ray(&r->p), (int)r->N, (int)s, r->segn.p);
+  if ((rc = srt_pack_rows_device(r->N, per, n, r->rows.p, r->segn.p, r->offsets.p, r->packed.p, n * (int64_t)r->N, nullptr))) return rc;
+  // (the launch has read its queue by the time the compaction overwrites it: one stream)
+  if ((rc = srt_running_rays_device(n, r->stop.p, r->queue.p, r->count.p, nullptr))) return rc;
+  r->all_off.resize((size_t)n + 1);
+  r->all_nrows.resize((size_t)n);
+  r->all_stop.resize((size_t)n);
+  int64_t c[4] = {0, 0, 0, 0};
+  int32_t next_nq = 0;
+  hipError_t e = hipMemcpy(r->all_off.data(), r->offsets.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(r->all_nrows.data(), r->nrows.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(r->all_stop.data(), r->stop.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(c, r->counters.p, sizeof c, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&next_nq, r->count.p, sizeof next_nq, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "trace segment %d failed: %s", (int)s, hipGetErrorString(e));
+  const int64_t total = r->all_off[(size_t)n];
+  if (total < 0 || total > n * (int64_t)r->N) return srt_set_error(SRT_EDEVICE, "trace segment %d: %lld packed rows for room of %lld", (int)s, (long long)total, (long long)(n * (int64_t)r->N));
+  r->h_rows.resize((size_t)total * SRT_ROW);
+  if (total > 0) HIP_OK(hipMemcpy(r->h_rows.data(), r->packed.p, (size_t)total * SRT_ROW * sizeof(double), hipMemcpyDeviceToHost));
+  // the rays that ran: all of them in segment 0, else the queue the previous call brought back.  Rays outside the queue keep
+  // no row in this segment, so the offsets of the whole set, read at the queue's ids, are the queue's own prefix sums.
+  r->ray.resize((size_t)nq);
+  r->h_off.resize((size_t)nq + 1);
+  r->h_nrows.resize((size_t)nq);
+  r->h_stop.resize((size_t)nq);
+  for (int64_t i = 0; i < nq; ++i) {
+    const int32_t id = s > 0 ? r->hq[(size_t)i] : (int32_t)i;
+    r->ray[(size_t)i] = id;
+    r->h_off[(size_t)i] = r->all_off[(size_t)id];
+    r->h_nrows[(size_t)i] = r->all_nrows[(size_t)id];
+    r->h_stop[(size_t)i] = r->all_stop[(size_t)id];
+  }
+  r->h_off[(size_t)nq] = total;
+  r->hq.resize((size_t)next_nq);
+  if (next_nq > 0) HIP_OK(hipMemcpy(r->hq.data(), r->queue.p, (size_t)next_nq * sizeof(int32_t), hipMemcpyDeviceToHost));
+  r->nq = next_nq;
+  r->seg = s + 1;
+  seg->segment = s;
+  seg->nrays = nq;
+  seg->ray = r->ray.data();
+  seg->offsets = r->h_off.data();
+  seg->rows = r->h_rows.data();
+  seg->nrows = r->h_nrows.data();
+  seg->stopcond = r->h_stop.data();
+  seg->accepted_steps = c[1];
+  return 1;
+}
+
+extern "C" void srt_trace_run_close(srt_trace_run *r) {
+  if (!r) return;
+  DeviceScope scope;
+  (void)scope.enter(r->device); // the buffers are freed on the device they live on
+  delete r;
 }

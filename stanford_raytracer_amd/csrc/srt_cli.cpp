@@ -194,6 +194,9 @@ int main(int argc, char **argv) {
          "           --use_tsyganenko=0: the model's field-line trace always runs through T04_s + IGRF)\n"
          "           --use_tsyganenko=0|1 --use_igrf=0|1 [--igrf_coeffs=<table>]\n"
          "  extra:   --device=N | --devices=0,1,..  --chunk_rays=N  --ray_order=0|1  --timing=1 (wall clock per phase)\n"
+         "           --segment_rows=N: trace in segments of N kept rows per ray and launch (rays are paused and resumed; device\n"
+         "             memory for chunk_rays * N rows instead of chunk_rays * maxsteps / outputper, the same .ray file; chunks of\n"
+         "             262144 rays unless --chunk_rays says otherwise; not together with --damping_out).  0 / absent: one launch per chunk\n"
          "           --first_attempt_policy=1|0: error estimate of a ray's first adaptive attempt, where the reference reads an\n"
          "             unset variable: 1 (default) = from the k term alone, as the reference's gfortran build behaves;\n"
          "             0 = NaN => accepted at dt0, dt not grown, as a flang build behaves (the goldens of this repository)\n"
@@ -453,6 +456,21 @@ int main(int argc, char **argv) {
   }
   get_int("ray_order", p.ray_order);
   get_int("chunk_rays", chunk);
+  // ours: --segment_rows=N, the trace in segments (include/srt.h); 0 = one launch per chunk with every slot up front
+  int segment_rows = 0;
+  get_int("segment_rows", segment_rows);
+  if (segment_rows < 0) {
+    fprintf(stderr, "raytracer: --segment_rows must be >= 0\n");
+    return 2;
+  }
+  {
+    std::string dummy;
+    if (segment_rows > 0 && getopt_named("damping_out", dummy)) {
+      fprintf(stderr, "raytracer: --damping_out together with --segment_rows is not supported: the damping's running magnitude needs "
+                      "the padded row layout of an unsegmented trace (run without --segment_rows, or --damping_in on the .ray file)\n");
+      return 2;
+    }
+  }
   // ours: --devices=0,1,.. = one host thread and one model replica per GPU, contiguous shards of the ray file
   // (ceil(n/ndev) rays each), records written in ray order.  Default: the one device of --device.
   std::vector<int> devices;
@@ -559,6 +577,77 @@ int main(int argc, char **argv) {
       if (rc) fprintf(stderr, "raytracer: writing %s failed\n", sh.out.c_str());
       return rc;
     };
+    if (segment_rows > 0) {
+      // The trace in segments: a chunk's rays go through the iterator, its rows are gathered ray-major on the host and written
+      // from the packed layout -- the records of the unsegmented run.  N is at most what a ray can keep.
+      const int32_t N = segment_rows < slots ? segment_rows : slots;
+      const int32_t nseg = srt_trace_segments(&q, N);
+      int64_t segchunk = chunk > 0 ? chunk : 262144;
+      if (chunk <= 0) segchunk = std::min<int64_t>(segchunk, ((int64_t)2 << 30) / ((int64_t)N * SRT_ROW * 8));
+      if (segchunk < 64) segchunk = 64;
+      struct Packed {
+        std::vector<int64_t> offsets;
+        std::vector<double> rows;
+        std::vector<int32_t> stop;
+      };
+      struct Piece { // one segment's delivery, kept until the chunk is assembled
+        std::vector<int32_t> ray;
+        std::vector<int64_t> offsets;
+        std::vector<double> rows;
+      };
+      for (int64_t lo = sh.lo; lo < sh.hi; lo += segchunk) {
+        const int64_t n = std::min<int64_t>(sh.hi - lo, segchunk);
+        auto c = std::make_shared<Packed>();
+        c->offsets.assign((size_t)n + 1, 0);
+        c->stop.assign((size_t)n, 0);
+        std::vector<Piece> pieces;
+        const double tt0 = now_s();
+        srt_trace_run *run = nullptr;
+        CHECK(srt_trace_run_open(m, &q, n, pos0 + 3 * lo, dir0 + 3 * lo, w0 + lo, N, &run));
+        for (int32_t s = 0; s < nseg; ++s) { // (bounded by the segment count, never by "until nothing is left" alone)
+          srt_segment sg;
+          const int got = srt_trace_run_next(run, &sg);
+          if (got < 0) {
+            fprintf(stderr, "raytracer: srt_trace_run_next failed: %s\n", srt_last_error());
+            srt_trace_run_close(run);
+            return 1;
+          }
+          if (got == 0) break;
+          Piece pc;
+          pc.ray.assign(sg.ray, sg.ray + sg.nrays);
+          pc.offsets.assign(sg.offsets, sg.offsets + sg.nrays + 1);
+          pc.rows.assign(sg.rows, sg.rows + (size_t)sg.offsets[sg.nrays] * SRT_ROW);
+          for (int64_t i = 0; i < sg.nrays; ++i) {
+            c->offsets[(size_t)sg.ray[i] + 1] += sg.offsets[i + 1] - sg.offsets[i]; // (counts first, prefix sums below)
+            c->stop[(size_t)sg.ray[i]] = sg.stopcond[i];
+          }
+          sh.steps += sg.accepted_steps;
+          pieces.push_back(std::move(pc));
+        }
+        srt_trace_run_close(run);
+        for (int64_t i = 0; i < n; ++i) c->offsets[(size_t)i + 1] += c->offsets[(size_t)i];
+        c->rows.resize((size_t)c->offsets[(size_t)n] * SRT_ROW);
+        std::vector<int64_t> fill(c->offsets.begin(), c->offsets.end() - 1); // where a ray's next rows go
+        for (const Piece &pc : pieces)
+          for (size_t i = 0; i < pc.ray.size(); ++i) {
+            const int64_t cnt = pc.offsets[i + 1] - pc.offsets[i];
+            if (cnt > 0) memcpy(c->rows.data() + (size_t)fill[(size_t)pc.ray[i]] * SRT_ROW, pc.rows.data() + (size_t)pc.offsets[i] * SRT_ROW, (size_t)cnt * SRT_ROW * sizeof(double));
+            fill[(size_t)pc.ray[i]] += cnt;
+          }
+        pieces.clear();
+        sh.trace_s += now_s() - tt0;
+        if (int rc = finish()) return rc;
+        pending = std::async(std::launch::async, [=, &sh]() -> int {
+          const double tw0 = now_s();
+          if (srt_write_ray_file_packed(sh.out.c_str(), 1, lo + 1, n, nspec, qs, ms, w0 + lo, c->offsets.data(), c->rows.data(), c->stop.data())) return 1;
+          sh.write_s += now_s() - tw0;
+          return 0;
+        });
+      }
+      if (int rc = finish()) return rc;
+      srt_model_destroy(m);
+      return 0;
+    }
     for (int64_t lo = sh.lo; lo < sh.hi; lo += maxchunk) {
       int64_t n = sh.hi - lo < maxchunk ? sh.hi - lo : maxchunk;
       auto c = std::make_shared<Chunk>();

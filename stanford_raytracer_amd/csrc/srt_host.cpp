@@ -729,17 +729,17 @@ static inline void put_es24(double v, char *out) {
 // Records are fixed-length (raytracer_driver.f95:1197-1217: i10, i10, 17 es24.15e3, i10, 4 nspec es24.15e3, newline), so a
 // ray's file offset is known from the kept-row counts before it: all host cores format disjoint ray ranges and pwrite them
 // in place (SRT_IO_THREADS=1: one thread).  At BASELINE config[2] (1 M rays, 13 kept rows each) the file is 10.7 GB of text.
-extern "C" int srt_write_ray_file(const char *path, int append, int64_t raynum0, int64_t nrays, const srt_params *p,
-                                  int nspec, const double *qs, const double *ms, const double *w0,
-                                  const double *rows, const int32_t *nrows, const int32_t *stopcond) {
-  if (!path || !p || !qs || !ms || !w0 || !rows || !nrows || !stopcond) return srt_set_error(SRT_EINVAL, "null argument");
+// The one formatting routine of both writers: prefix[r] = records before ray r (prefix[nrays] = all of them), and record s
+// of ray r is the row at rows + (r * stride + prefix[r] * packed + s) * SRT_ROW -- stride = slots, packed = 0 for the padded
+// layout [nrays][slots][SRT_ROW]; stride = 0, packed = 1 for rows that lie back to back.
+static int write_ray_records(const char *path, int append, int64_t raynum0, int64_t nrays, int nspec, const double *qs,
+                             const double *ms, const double *w0, const double *rows, const int32_t *stopcond,
+                             const std::vector<int64_t> &prefix, size_t stride, size_t packed) {
   if (nspec < 1 || nspec > SRT_MAXSPEC) return srt_set_error(SRT_EINVAL, "nspec out of range");
   // the record's ray number is an i10 field (raytracer_driver.f95:1197): beyond ten digits Fortran prints asterisks and the
   // fixed-length record could not hold the number -- refused rather than shifted or truncated
   if (raynum0 < 0 || nrays < 0 || raynum0 + nrays - 1 > 9999999999ll)
     return srt_set_error(SRT_EINVAL, "ray numbers %lld .. %lld do not fit the record's i10 field", (long long)raynum0, (long long)(raynum0 + nrays - 1));
-  const int slots = srt_rows_per_ray(p);
-  const int per = p->outputper < 1 ? 1 : p->outputper;
   const size_t L = 20 + 17 * 24 + 10 + (size_t)4 * nspec * 24 + 1;
   const int fd = open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
   if (fd < 0) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
@@ -748,18 +748,12 @@ extern "C" int srt_write_ray_file(const char *path, int append, int64_t raynum0,
     struct stat st;
     if (fstat(fd, &st) == 0) base = st.st_size;
   }
-  auto kept_of = [&](int64_t r) {
-    int k = (nrows[r] + per - 1) / per;
-    return k > slots ? slots : (k < 0 ? 0 : k);
-  };
   int nth = (int)std::thread::hardware_concurrency();
   if (const char *e = getenv("SRT_IO_THREADS")) nth = atoi(e);
   if (nth < 1) nth = 1;
   if (nth > 64) nth = 64;
   if ((int64_t)nth > nrays) nth = nrays > 0 ? (int)nrays : 1;
-  // contiguous ray ranges, one per thread; prefix[r] = records before ray r
-  std::vector<int64_t> prefix((size_t)nrays + 1, 0);
-  for (int64_t r = 0; r < nrays; ++r) prefix[r + 1] = prefix[r] + kept_of(r);
+  // contiguous ray ranges, one per thread
   std::vector<int64_t> first(nth + 1);
   for (int t = 0; t <= nth; ++t) first[t] = (nrays * t) / nth;
   std::vector<char> consts((size_t)8 * 24); // qs and ms of the record, formatted once
@@ -790,12 +784,12 @@ extern "C" int srt_write_ray_file(const char *path, int append, int64_t raynum0,
       fill = 0;
     };
     for (int64_t r = first[t]; r < first[t + 1] && !fail[t]; ++r) {
-      const int kept = kept_of(r);
+      const int64_t kept = prefix[r + 1] - prefix[r];
       char head[24], wbuf[24];
       snprintf(head, sizeof head, "%10lld%10d", (long long)(raynum0 + r), (int)stopcond[r]);
       put_es24(w0[r], wbuf);
-      for (int s = 0; s < kept; ++s) {
-        const double *row = rows + ((size_t)r * slots + s) * SRT_ROW;
+      for (int64_t s = 0; s < kept; ++s) {
+        const double *row = rows + ((size_t)r * stride + (size_t)prefix[r] * packed + (size_t)s) * SRT_ROW;
         char *q = buf.data() + fill;
         memcpy(q, head, 20);
         q += 20;
@@ -828,6 +822,33 @@ extern "C" int srt_write_ray_file(const char *path, int append, int64_t raynum0,
     if (fail[t]) return srt_set_error(SRT_EIO, "%s: write failed", path);
   if (rc != 0) return srt_set_error(SRT_EIO, "%s: close failed", path);
   return SRT_OK;
+}
+
+extern "C" int srt_write_ray_file(const char *path, int append, int64_t raynum0, int64_t nrays, const srt_params *p,
+                                  int nspec, const double *qs, const double *ms, const double *w0,
+                                  const double *rows, const int32_t *nrows, const int32_t *stopcond) {
+  if (!path || !p || !qs || !ms || !w0 || !rows || !nrows || !stopcond) return srt_set_error(SRT_EINVAL, "null argument");
+  const int slots = srt_rows_per_ray(p);
+  const int per = p->outputper < 1 ? 1 : p->outputper;
+  std::vector<int64_t> prefix(nrays > 0 ? (size_t)nrays + 1 : 1, 0); // (nrays < 0 is refused by the shared routine)
+  for (int64_t r = 0; r < nrays; ++r) {
+    const int k = (nrows[r] + per - 1) / per;
+    prefix[r + 1] = prefix[r] + (k > slots ? slots : (k < 0 ? 0 : k));
+  }
+  return write_ray_records(path, append, raynum0, nrays, nspec, qs, ms, w0, rows, stopcond, prefix, (size_t)slots, 0);
+}
+
+// the same file from the packed layout srt_read_ray_file returns: offsets[nrays + 1], rows[offsets[nrays]][SRT_ROW]
+extern "C" int srt_write_ray_file_packed(const char *path, int append, int64_t raynum0, int64_t nrays, int nspec, const double *qs,
+                                         const double *ms, const double *w0, const int64_t *offsets, const double *rows,
+                                         const int32_t *stopcond) {
+  if (!path || !qs || !ms || !offsets || nrays < 0 || (nrays > 0 && (!w0 || !stopcond))) return srt_set_error(SRT_EINVAL, "null argument");
+  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
+  for (int64_t r = 0; r < nrays; ++r)
+    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "offsets decrease at ray %lld", (long long)r);
+  if (offsets[nrays] > 0 && !rows) return srt_set_error(SRT_EINVAL, "null argument");
+  const std::vector<int64_t> prefix(offsets, offsets + nrays + 1);
+  return write_ray_records(path, append, raynum0, nrays, nspec, qs, ms, w0, rows, stopcond, prefix, 0, 1);
 }
 
 // ---- frame rotation SM <-> MAG (xform_double's sm_to_mag_d / mag_to_sm_d; srt_xform.hpp) ----

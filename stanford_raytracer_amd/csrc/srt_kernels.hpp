@@ -63,6 +63,19 @@ struct TraceArgs {
   double *scratch2;   // scattered model: candidate blocks, ScatteredModel::BLOCK_DOUBLES doubles per block (or nullptr)
   TraceParams p;
 };
+// what a segmented launch (trace_kernel<.., SEG = true>) takes: the same, and behind it (no existing member moves, and the
+// unsegmented kernels' argument block is the one it was)
+struct TraceSegArgs : TraceArgs {
+  double *state;      // [nrays][TRACE_STATE]: the integrator state of paused rays
+  long long nqueue;   // rays in this launch's queue (`order` holds their ids; nullptr = rays 0 .. nqueue - 1)
+  int seg_rows;       // N: kept rows per ray and launch = slots of a ray in `rows`
+  int segment;        // s: this launch owns row indices [s N outputper, (s + 1) N outputper)
+};
+__device__ __forceinline__ int segment_of(const TraceArgs &) { return 0; }
+__device__ __forceinline__ int segment_of(const TraceSegArgs &a) { return a.segment; }
+// A paused ray's record: x[6], r1[6] (the carried first stage), vg[3], t, dt (srt.h: SRT_STATE).  nstep travels in nrows;
+// lastrefinedown is 0 and first_attempt is nstep == 1 wherever a ray can pause.
+constexpr int TRACE_STATE = 17;
 
 // Stencil of raytracer_evalrhs: centre + the six points x +- d e_c of dispersion_relation_dFdx
 // (raytracer.f95:239-262).  p[0] centre, p[1+2c] = x + d_c e_c, p[2+2c] = x - d_c e_c.
@@ -348,8 +361,13 @@ __device__ __forceinline__ void store_row(double *row, double t, const double x[
 // raytracer_run for a whole launch set (raytracer.f95:609-995 x the driver loop :1144-1232).
 // FOPT: field option fixed at compile time -- 0 dipole, 1 IGRF main field alone, 2 the general tail (T04_s on an IGRF or
 // dipole base, chosen at run time inside)
-template <class M, bool FIXED, bool USE_LDS, int FOPT = 0>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M>::WAVES_PER_EU))) void trace_kernel(const M *__restrict__ mp, const Common *__restrict__ cp, TraceArgs a) {
+// SEG: one segment of a launch set traced in segments (srt_trace_segment_device).  Segment s keeps the rows of its own index
+// range in a[nrays][N][ROW] and, at the loop top behind the reference's own stop tests, parks every ray that has reached the
+// range's end: state record, nrows = nstep, stopcond = -1.  In segment 0 the queue's rays are launched as ever; in a later
+// segment they are restored from their records and go straight to `active` (no ride-along trip, no row 0), so a ray's
+// arithmetic is that of the unsegmented launch.  counters[1] counts the steps accepted in THIS launch.
+template <class M, bool FIXED, bool USE_LDS, int FOPT = 0, bool SEG = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M>::WAVES_PER_EU))) void trace_kernel(const M *__restrict__ mp, const Common *__restrict__ cp, typename std::conditional<SEG, TraceSegArgs, TraceArgs>::type a) {
   const M &m = *mp;
   constexpr bool IGRF = FOPT != 0;
   typedef typename std::conditional<FOPT == 0, CommonDipole, typename std::conditional<FOPT == 1, CommonIgrfOnly, CommonIgrf>::type>::type CM;
@@ -375,6 +393,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
   bool first_attempt = true;
   unsigned long long acc_steps = 0, acc_attempts = 0, wave_trips = 0;
   const int threshold = P.refill_threshold > 0 ? P.refill_threshold : 1;
+  long long nwork = a.nrays; // rays in the queue
+  if constexpr (SEG) nwork = a.nqueue;
 #ifdef SRT_PHASE_TIMING
   const unsigned long long srt_wave_t0 = __builtin_readcyclecounter();
 #endif
@@ -400,6 +420,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
         active = false;
       }
     }
+    if constexpr (SEG) {
+      // pause: the next row this ray produces belongs to a later segment (a ray at maxsteps has stopped above)
+      if (active && (long long)nstep >= ((long long)a.segment + 1) * a.seg_rows * P.outputper) {
+        double *s = a.state + (size_t)ray * TRACE_STATE;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          s[c] = x[c];
+          s[6 + c] = r1[c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[12 + c] = vg[c];
+        s[15] = t;
+        s[16] = dt;
+        a.nrows[ray] = nstep;
+        a.stopcond[ray] = -1; // SRT_RUNNING
+        acc_steps += (unsigned long long)(nstep - 1);
+        active = false;
+      }
+    }
     // ---- B. refill free lanes from the queue (ballot compaction)
     unsigned long long freemask = __ballot(!active);
     int nfree = __popcll(freemask);
@@ -412,21 +451,45 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
       if (!active) {
         int rank = __popcll(freemask & ((1ull << lane) - 1ull));
         long long id = (long long)base + rank;
-        if (rank < take && id < a.nrays) {
+        if (rank < take && id < nwork) {
           if (a.order) id = a.order[id];
           ray = id;
-          needinit = true;
-          new_ray_hook(m, lds, true);
-          x[0] = a.pos0[id];
-          x[1] = a.pos0[a.nrays + id];
-          x[2] = a.pos0[2 * a.nrays + id];
-          dirv[0] = a.dir0[id];
-          dirv[1] = a.dir0[a.nrays + id];
-          dirv[2] = a.dir0[2 * a.nrays + id];
-          w = a.w0[id];
+          // a later segment (wave-uniform): the queue holds paused rays, restored from their records.  (`SEG &&` is a constant
+          // the compiler folds where it stands: the unsegmented kernels have no branch here.)
+          if (SEG && segment_of(a) > 0) {
+            if constexpr (SEG) {
+              new_ray_hook(m, lds, true);
+              const double *s = a.state + (size_t)id * TRACE_STATE;
+#pragma unroll
+              for (int c = 0; c < 6; ++c) {
+                x[c] = s[c];
+                r1[c] = s[6 + c];
+              }
+#pragma unroll
+              for (int c = 0; c < 3; ++c) vg[c] = s[12 + c];
+              t = s[15];
+              dt = s[16];
+              nstep = a.nrows[id];
+              lastrefinedown = 0;
+              first_attempt = nstep == 1;
+              w = a.w0[id];
+              acc_steps -= (unsigned long long)(nstep - 1); // (counted again, with this launch's steps, when the ray pauses or stops)
+              active = true;
+            }
+          } else {
+            needinit = true;
+            new_ray_hook(m, lds, true);
+            x[0] = a.pos0[id];
+            x[1] = a.pos0[a.nrays + id];
+            x[2] = a.pos0[2 * a.nrays + id];
+            dirv[0] = a.dir0[id];
+            dirv[1] = a.dir0[a.nrays + id];
+            dirv[2] = a.dir0[2 * a.nrays + id];
+            w = a.w0[id];
+          }
         }
       }
-      if ((long long)base + take >= a.nrays) queue_empty = true;
+      if ((long long)base + take >= nwork) queue_empty = true;
     }
     // ---- C. (newly claimed rays have no step of their own this trip: they ride along with the running ones and
     // their launch point takes the place of the step's end point in E/F/G, see there; :661-742.  Every ray is
@@ -605,7 +668,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
 #pragma unroll
         for (int c = 0; c < 3; ++c) vp[c] = vg[c] = 0.0;
       }
-      store_row(a.rows + (size_t)ray * (size_t)P.slots * ROW, t, x, vp, vg, n, ps2);
+      int stride = P.slots; // slots of a ray in the row buffer
+      if constexpr (SEG) stride = a.seg_rows;
+      store_row(a.rows + (size_t)ray * (size_t)stride * ROW, t, x, vp, vg, n, ps2);
       active = true;
       needinit = false;
     } else if (active && !reject) {
@@ -655,7 +720,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
         const int row = nstep - 1;
         if (finite && row % P.outputper == 0) {
           int slot = row / P.outputper;
-          if (slot < P.slots)
+          if constexpr (SEG) {
+            const int local = slot - a.segment * a.seg_rows; // (0 <= local < N by the pause test; checked all the same)
+            if (slot < P.slots && local >= 0 && local < a.seg_rows)
+              store_row(a.rows + ((size_t)ray * (size_t)a.seg_rows + (size_t)local) * ROW, t, x, vp, vg, n, ps2);
+          } else if (slot < P.slots)
             store_row(a.rows + ((size_t)ray * (size_t)P.slots + (size_t)slot) * ROW, t, x, vp, vg, n, ps2);
         }
       }

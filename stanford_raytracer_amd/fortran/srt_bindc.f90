@@ -22,6 +22,14 @@ module srt_bindc
      integer(c_int32_t) :: m(8)
      real(c_double) :: Ne_h, kT, tol
   end type srt_damping_params
+  ! srt_segment: what one srt_trace_run_next hands out (valid until the next call on the run).  c_f_pointer turns the members
+  ! into arrays: ray(nrays), offsets(nrays+1), rows(20, offsets(nrays+1)), nrows(nrays), stopcond(nrays)
+  type, bind(C) :: srt_segment
+     integer(c_int32_t) :: segment, reserved
+     integer(c_int64_t) :: nrays
+     type(c_ptr) :: ray, offsets, rows, nrows, stopcond
+     integer(c_int64_t) :: accepted_steps
+  end type srt_segment
 
   interface
      integer(c_int) function srt_init(device) bind(C, name="srt_init")
@@ -193,6 +201,43 @@ module srt_bindc
        integer(c_int32_t) :: nrows(*), stopcond(*)
        integer(c_int64_t) :: accepted_steps
      end function srt_trace_batch
+     ! the same rays traced in segments of segment_rows kept rows per ray and launch (include/srt.h): open, next until it
+     ! returns 0 (at most srt_trace_segments times), close
+     integer(c_int32_t) function srt_trace_segments(p, segment_rows) bind(C, name="srt_trace_segments")
+       import :: c_int32_t, srt_params
+       type(srt_params) :: p
+       integer(c_int32_t), value :: segment_rows
+     end function srt_trace_segments
+     integer(c_int) function srt_trace_run_open(model, p, nrays, pos0, dir0, w0, segment_rows, run) &
+          bind(C, name="srt_trace_run_open")
+       import :: c_int, c_ptr, c_double, c_int64_t, c_int32_t, srt_params
+       type(c_ptr), value :: model
+       type(srt_params) :: p
+       integer(c_int64_t), value :: nrays
+       real(c_double), intent(in) :: pos0(3,*), dir0(3,*), w0(*)
+       integer(c_int32_t), value :: segment_rows
+       type(c_ptr) :: run
+     end function srt_trace_run_open
+     integer(c_int) function srt_trace_run_next(run, seg) bind(C, name="srt_trace_run_next")
+       import :: c_int, c_ptr, srt_segment
+       type(c_ptr), value :: run
+       type(srt_segment) :: seg
+     end function srt_trace_run_next
+     subroutine srt_trace_run_close(run) bind(C, name="srt_trace_run_close")
+       import :: c_ptr
+       type(c_ptr), value :: run
+     end subroutine srt_trace_run_close
+     ! the .ray file from packed rows: offsets(nrays+1), rows(20, offsets(nrays+1))
+     integer(c_int) function srt_write_ray_file_packed(path, append, raynum0, nrays, nspec, qs, ms, w0, offsets, rows, &
+          stopcond) bind(C, name="srt_write_ray_file_packed")
+       import :: c_int, c_char, c_double, c_int64_t, c_int32_t
+       character(kind=c_char), dimension(*) :: path
+       integer(c_int), value :: append, nspec
+       integer(c_int64_t), value :: raynum0, nrays
+       real(c_double), intent(in) :: qs(*), ms(*), w0(*), rows(*)
+       integer(c_int64_t), intent(in) :: offsets(*)
+       integer(c_int32_t), intent(in) :: stopcond(*)
+     end function srt_write_ray_file_packed
      integer(c_int64_t) function srt_read_rays_file(path, pos0, dir0, w0) bind(C, name="srt_read_rays_file")
        import :: c_int64_t, c_char, c_ptr
        character(kind=c_char), dimension(*) :: path
