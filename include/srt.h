@@ -423,6 +423,54 @@ int srt_damping_device(const srt_damping_params *dp, int nspec, const double *qs
                        int32_t outputper, int64_t nrays, const double *d_rows, const int32_t *d_nrows,
                        const double *d_w0, double *d_rate, double *d_magnitude, int32_t *d_flag, void *stream);
 
+/* ---- surface crossings along the kept rows: where and when each ray crosses a surface ----
+ * No piece of the reference does this (matlab/ only plots); it is what users of many rays do next, on the device instead of a
+ * host loop over the rows or a .ray file.  Input is the PACKED layout that srt_pack_rows_device, a segmented trace and
+ * srt_read_ray_file produce: offsets[nrays + 1] (offsets[0] = 0) and rows[offsets[nrays]][SRT_ROW].
+ * g(x) of a surface, x in SM metres as the rows are (R_E = 6371.2e3):
+ *   kind 0, sphere             g = |x| - p[0]
+ *   kind 1, dipole L-shell     g = |x|^3 - p[0] R_E (x^2 + y^2)      (no division on the axis; g > 0 <=> L > p[0])
+ *   kind 2, magnetic latitude  g = z - |x| sin(p[0])                 (p[0] in radians; the sine is taken once, on the host)
+ *   kind 3, plane              g = p[0] x + p[1] y + p[2] z - p[3]
+ * The interval (i, i + 1) of a ray's consecutive kept rows holds an EVENT of surface s when (g_i < 0) != (g_{i+1} < 0): a row
+ * exactly on the surface gives one event per pass, not two.  An interval with t_{i+1} == t_i, or with a non-finite t, pos or
+ * vgrel at either end, holds none; a ray with fewer than two rows has none.  SAMPLING: an interval in which g changes sign twice
+ * holds no event either -- the kept rows decide what can be seen, so outputper decides how often that happens.
+ * Between the rows the ray is the cubic Hermite curve whose end slopes are the rows' own C vgrel, the right-hand side of the
+ * position equation at the row (C as the models compute it, constants.f95:7).  With h = t1 - t0, D = p1 - p0, m0 = C vg0 h,
+ * m1 = C vg1 h:   p(sigma) = p0 + sigma m0 + sigma^2 (3 D - 2 m0 - m1) + sigma^3 (m0 + m1 - 2 D).
+ * Rows with vgrel = 0 (the n.n <= 0 rows) are used as they stand.  sigma* is a point of [0, 1] within 2^-50 of a sign change of
+ * g(p(sigma)) that has the interval's end signs either side of it: 52 bisections of [0, 1], of whose last bracket the end with
+ * g >= 0 is returned, deterministic, the same on host and device.
+ * An event is a row of SRT_ROW doubles in the kept-row layout (t = t0 + sigma* h, pos = p(sigma*), columns 4 .. 19 -- vprel,
+ * vgrel, n, B0, Ns -- linear in sigma*; srt_damping and the writers can take it as a row) and four int32: the ray, the surface's
+ * index, the interval i (0-based among the ray's kept rows), and the direction (+1: g goes from < 0 to >= 0, else -1).
+ * Events are ordered by (ray, interval, surface index).
+ * SRT_EINVAL, by name, before the device is looked at: nsurf outside 1 .. SRT_MAXSURF, an unknown kind, a non-finite parameter,
+ * a sphere radius <= 0, L <= 0, |latitude| >= pi/2, a zero plane normal; host offsets that decrease or do not start at 0. */
+#define SRT_MAXSURF 16
+typedef struct srt_surface {
+  int32_t kind;
+  int32_t reserved;
+  double p[4];
+} srt_surface;
+/* On buffers resident in device memory (`surfaces` is host memory).  d_event_rows[capacity][SRT_ROW], d_event_meta[capacity][4],
+ * d_count one int64: it always receives the total; events beyond `capacity` are left out (the first `capacity` events of the
+ * defined order are kept).  capacity = 0 with NULL outputs is a count-only call.  The device is found from the buffers, as in
+ * srt_pack_rows_device.  The call reads d_offsets[nrays] (8 bytes) behind the work already on `stream`, to size its launches,
+ * and checks it against the allocation d_rows points into; from there on it is asynchronous on `stream`. */
+int srt_crossings_device(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *d_offsets, const double *d_rows,
+                         double *d_event_rows, int32_t *d_event_meta, int64_t capacity, int64_t *d_count, void *stream);
+/* The same on host buffers; *event_rows[*nevents][SRT_ROW] and *event_meta[*nevents][4] are malloc'd (srt_free; NULL when there
+ * are no events). */
+int srt_crossings(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *offsets, const double *rows,
+                  int64_t *nevents, double **event_rows, int32_t **event_meta);
+/* One record per event, (4 i10, 20 es24.15e3): raynum[e] (the caller's number of the event's ray, e.g. raynum of
+ * srt_read_ray_file indexed by the event's ray), surface index + 1, interval + 1, direction, then the event's row, formatted as
+ * the .ray writer formats.  Pure host code, needs no GPU. */
+int srt_crossings_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
+                             const double *event_rows);
+
 /* ---- file formats of the boundary ---- */
 /* ray input file: 7 list-directed reals per line (raytracer_driver.f95:1146); returns count, fills
  * malloc'd arrays the caller frees with srt_free */

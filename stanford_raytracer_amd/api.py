@@ -61,6 +61,12 @@ class Segment(C.Structure):
                 ("accepted_steps", C.c_int64)]
 
 
+class Surface(C.Structure):
+    """srt_surface of include/srt.h: kind 0 sphere, 1 dipole L-shell, 2 magnetic latitude, 3 plane; see sphere() .. plane()."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 4)]
+
+
+MAXSURF = 16  # SRT_MAXSURF
 RUNNING = -1  # SRT_RUNNING: stopcond of a paused ray
 STATE = 17    # SRT_STATE: doubles in a paused ray's record
 
@@ -169,6 +175,10 @@ def lib():
     L.srt_sm_to_mag.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, dp, dp]
     L.srt_dump_file_write.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp]
     L.srt_dump_file_read.argtypes = [C.c_char_p, i32p, dp, C.POINTER(dp)]
+    i64p = C.POINTER(C.c_int64)
+    L.srt_crossings_device.argtypes = [C.c_int, C.POINTER(Surface), C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp]
+    L.srt_crossings.argtypes = [C.c_int, C.POINTER(Surface), C.c_int64, i64p, dp, i64p, C.POINTER(dp), C.POINTER(ip)]
+    L.srt_crossings_file_write.argtypes = [C.c_char_p, C.c_int64, i64p, ip, dp]
     _lib = L
     return L
 
@@ -660,6 +670,90 @@ def padded_rows(ray):
     for i in range(n):
         rows[i, :kept[i]] = ray["rows"][off[i]:off[i + 1]]
     return rows, kept.astype(np.int32)
+
+
+# ---- surface crossings along the kept rows (include/srt.h) -------
+R_E = 6371.2e3
+
+
+def sphere(r):
+    """|x| = r metres."""
+    return Surface(0, 0, (C.c_double * 4)(float(r), 0.0, 0.0, 0.0))
+
+
+def lshell(L):
+    """The dipole L-shell |x|^3 = L R_E (x^2 + y^2)."""
+    return Surface(1, 0, (C.c_double * 4)(float(L), 0.0, 0.0, 0.0))
+
+
+def maglat(rad):
+    """The cone of magnetic latitude `rad` radians (0: the magnetic equator)."""
+    return Surface(2, 0, (C.c_double * 4)(float(rad), 0.0, 0.0, 0.0))
+
+
+def plane(normal, d):
+    """normal . x = d."""
+    nx, ny, nz = (float(v) for v in normal)
+    return Surface(3, 0, (C.c_double * 4)(nx, ny, nz, float(d)))
+
+
+def surface_array(surfaces):
+    """A sequence of Surface -> (ctypes array, count), as the C ABI takes them."""
+    surfaces = list(surfaces)
+    arr = (Surface * max(len(surfaces), 1))()
+    for i, s in enumerate(surfaces):
+        arr[i] = s
+    return arr, len(surfaces)
+
+
+def crossings(offsets, rows, surfaces):
+    """Where and when the rays of a packed row set (offsets[n+1], rows[offsets[n], 20]: read_ray_file, Model.trace_packed) cross
+    `surfaces`, located on the cubic Hermite curve through consecutive kept rows -> (event_rows[E, 20], meta[E, 4] int32 =
+    ray, surface index, interval, direction), ordered by (ray, interval, surface)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    rows = _f64(rows).reshape(-1, ROW)
+    if offsets.ndim != 1 or offsets.size < 1:
+        raise ValueError("offsets holds nrays + 1 entries")
+    if rows.shape[0] < offsets[-1]:
+        raise ValueError("offsets name %d rows, rows holds %d" % (offsets[-1], rows.shape[0]))
+    arr, ns = surface_array(surfaces)
+    n, pe, pm = C.c_int64(), dp(), ip()
+    _check(lib().srt_crossings(ns, arr, offsets.size - 1, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(rows), C.byref(n),
+                               C.byref(pe), C.byref(pm)))
+    try:
+        ev = np.ctypeslib.as_array(pe, (n.value, ROW)).copy() if n.value else np.zeros((0, ROW))
+        meta = np.ctypeslib.as_array(pm, (n.value, 4)).copy() if n.value else np.zeros((0, 4), dtype=np.int32)
+    finally:
+        lib().srt_free(pe)
+        lib().srt_free(pm)
+    return ev, meta
+
+
+def pack_rows(rows, nrows, outputper):
+    """rows[n, slots, 20], nrows[n] as Model.trace returns them -> (offsets[n+1], packed[offsets[n], 20]), on the host."""
+    rows = _f64(rows)
+    n, slots, _ = rows.shape
+    nr = np.asarray(nrows, dtype=np.int64)
+    kept = np.clip(np.where(nr > 0, (nr - 1) // int(outputper) + 1, 0), 0, slots)
+    offsets = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+    return offsets, rows[np.arange(slots)[None, :] < kept[:, None]].reshape(-1, ROW)
+
+
+def crossings_padded(rows, nrows, outputper, surfaces):
+    """crossings() of rows[n, slots, 20], nrows[n] as Model.trace returns them: packs first."""
+    offsets, packed = pack_rows(rows, nrows, outputper)
+    return crossings(offsets, packed, surfaces)
+
+
+def write_crossings_file(path, raynum, meta, event_rows):
+    """One record per event, (4 i10, 20 es24.15e3): raynum[e], surface index + 1, interval + 1, direction, the event's row."""
+    meta = np.ascontiguousarray(meta, dtype=np.int32).reshape(-1, 4)
+    event_rows = _f64(event_rows).reshape(-1, ROW)
+    raynum = np.ascontiguousarray(raynum, dtype=np.int64).reshape(-1)
+    if not (len(raynum) == len(meta) == len(event_rows)):
+        raise ValueError("raynum, meta and event_rows name %d, %d and %d events" % (len(raynum), len(meta), len(event_rows)))
+    _check(lib().srt_crossings_file_write(os.fsencode(path), len(meta), raynum.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          meta.ctypes.data_as(ip), _dp(event_rows)))
 
 
 # ---- model-3 grid files: text of the reference's grid builder <-> binary side-format (host code, no GPU) -------

@@ -30,6 +30,7 @@
 #include "srt_sampler.hpp"
 #include "srt_damping.hpp"
 #include "srt_xform.hpp"
+#include "srt_crossings.hpp"
 #include <hipcub/hipcub.hpp>
 
 using namespace srt;
@@ -2157,6 +2158,141 @@ extern "C" int srt_pack_rows_device(int32_t slots, int32_t outputper, int64_t nr
                        (const long long *)d_offsets, d_packed, (long long)capacity_rows);
   }
   HIP_OK(hipGetLastError());
+  return SRT_OK;
+}
+
+// ---- surface crossings along packed rows (kernels and point functions: srt_crossings.hpp) ----
+// does [q, q + bytes) lie inside the allocation q points into?  (true when the runtime cannot say)
+static bool within_allocation(const void *q, size_t bytes) {
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)q) != hipSuccess) {
+    (void)hipGetLastError();
+    return true;
+  }
+  return (const char *)q + bytes <= (const char *)base + size;
+}
+
+extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *d_offsets,
+                                    const double *d_rows, double *d_event_rows, int32_t *d_event_meta, int64_t capacity,
+                                    int64_t *d_count, void *stream) {
+  namespace cx = srt::crossings;
+  cx::Surfaces S;
+  char why[200];
+  if (cx::prepare(nsurf, surfaces, &S, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_crossings_device: %s", why);
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_crossings_device: nrays = %lld is negative", (long long)nrays);
+  if (nrays >= (1ll << 31)) return srt_set_error(SRT_EINVAL, "srt_crossings_device: nrays = %lld: an event names its ray in an int32", (long long)nrays);
+  if (capacity < 0) return srt_set_error(SRT_EINVAL, "srt_crossings_device: capacity = %lld is negative", (long long)capacity);
+  if (!d_offsets || !d_count) return srt_set_error(SRT_EINVAL, "srt_crossings_device: null d_offsets or d_count");
+  if (capacity > 0 && (!d_event_rows || !d_event_meta)) return srt_set_error(SRT_EINVAL, "srt_crossings_device: capacity = %lld with a null output", (long long)capacity);
+  int dev = -1, rc;
+  {
+    const void *ptrs[5] = {d_offsets, d_count, d_rows, capacity > 0 ? (const void *)d_event_rows : nullptr,
+                           capacity > 0 ? (const void *)d_event_meta : nullptr};
+    if ((rc = device_of("srt_crossings_device", ptrs, 5, &dev))) return rc;
+  }
+  DeviceScope scope;
+  if ((rc = scope.enter(dev))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!within_allocation(d_offsets, ((size_t)nrays + 1) * sizeof(int64_t)))
+    return srt_set_error(SRT_EINVAL, "srt_crossings_device: d_offsets has no room for nrays + 1 = %lld entries", (long long)nrays + 1);
+  // the one thing the host has to know: how many rows there are
+  long long total = 0;
+  HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (total < 0) return srt_set_error(SRT_EINVAL, "srt_crossings_device: offsets[nrays] = %lld is negative", total);
+  if (total >= (1ll << 31) - 1) return srt_set_error(SRT_EINVAL, "srt_crossings_device: %lld rows are too many for one call (2^31 - 2 at most)", total);
+  if (total < 2) { // no interval
+    HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
+    return SRT_OK;
+  }
+  if (!d_rows) return srt_set_error(SRT_EINVAL, "srt_crossings_device: null d_rows");
+  if (!within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double)))
+    return srt_set_error(SRT_EINVAL, "srt_crossings_device: offsets[nrays] names %lld rows, more than the allocation of d_rows holds", total);
+  if (capacity > 0 && (!within_allocation(d_event_rows, (size_t)capacity * SRT_ROW * sizeof(double)) ||
+                       !within_allocation(d_event_meta, (size_t)capacity * 4 * sizeof(int32_t))))
+    return srt_set_error(SRT_EINVAL, "srt_crossings_device: an output has no room for capacity = %lld events", (long long)capacity);
+  // scratch on the stream: mask[total] (2 B a row), evoff[total + 1] (8 B a row), the scan's own
+  static_assert(sizeof(long long) == sizeof(int64_t), "int64");
+  uint16_t *mask = nullptr;
+  long long *evoff = nullptr;
+  void *tmp = nullptr;
+  HIP_OK(hipMallocAsync((void **)&evoff, ((size_t)total + 1) * sizeof(long long), st));
+  hipError_t e = hipMallocAsync((void **)&mask, (size_t)total * sizeof(uint16_t), st);
+  size_t need = 0;
+  auto counts = hipcub::TransformInputIterator<long long, cx::MaskCount, hipcub::CountingInputIterator<long long>>(
+      hipcub::CountingInputIterator<long long>(0), cx::MaskCount{mask, total});
+  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, evoff, (int)(total + 1), st);
+  if (e == hipSuccess) e = hipMallocAsync(&tmp, need ? need : 16, st);
+  if (e == hipSuccess) {
+    long long blocks = (total + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(cx::crossings_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, S, (long long)nrays,
+                       (const long long *)d_offsets, total, d_rows, mask);
+    e = hipcub::DeviceScan::ExclusiveSum(tmp, need, counts, evoff, (int)(total + 1), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_count, evoff + total, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && capacity > 0)
+      hipLaunchKernelGGL(cx::crossings_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, st, S, (long long)nrays,
+                         (const long long *)d_offsets, total, d_rows, (const uint16_t *)mask, (const long long *)evoff,
+                         (long long)capacity, d_event_rows, d_event_meta);
+    if (e == hipSuccess) e = hipGetLastError();
+  }
+  // (also on the error path)
+  if (tmp) (void)hipFreeAsync(tmp, st);
+  if (mask) (void)hipFreeAsync(mask, st);
+  (void)hipFreeAsync(evoff, st);
+  HIP_OK(e);
+  return SRT_OK;
+}
+
+extern "C" int srt_crossings(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *offsets, const double *rows,
+                             int64_t *nevents, double **event_rows, int32_t **event_meta) {
+  namespace cx = srt::crossings;
+  cx::Surfaces S;
+  char why[200];
+  if (cx::prepare(nsurf, surfaces, &S, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_crossings: %s", why);
+  if (!nevents || !event_rows || !event_meta) return srt_set_error(SRT_EINVAL, "srt_crossings: null output");
+  *nevents = 0;
+  *event_rows = nullptr;
+  *event_meta = nullptr;
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_crossings: nrays = %lld is negative", (long long)nrays);
+  if (!offsets) return srt_set_error(SRT_EINVAL, "srt_crossings: null offsets");
+  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_crossings: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
+  for (int64_t r = 0; r < nrays; ++r)
+    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_crossings: offsets decrease at ray %lld", (long long)r);
+  const int64_t total = offsets[nrays];
+  if (total > 0 && !rows) return srt_set_error(SRT_EINVAL, "srt_crossings: null rows");
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  if (total < 2) return SRT_OK;
+  DevBuf<double> d_rows, d_ev;
+  DevBuf<int64_t> d_off, d_count;
+  DevBuf<int32_t> d_meta;
+  if ((rc = upload(d_rows, rows, (size_t)total * SRT_ROW))) return rc;
+  HIP_OK(d_off.alloc((size_t)nrays + 1));
+  HIP_OK(d_count.alloc(1));
+  HIP_OK(hipMemcpy(d_off.p, offsets, ((size_t)nrays + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if ((rc = srt_crossings_device(nsurf, surfaces, nrays, d_off.p, d_rows.p, nullptr, nullptr, 0, d_count.p, nullptr))) return rc;
+  int64_t n = 0;
+  HIP_OK(hipMemcpy(&n, d_count.p, sizeof n, hipMemcpyDeviceToHost));
+  if (n == 0) return SRT_OK;
+  HIP_OK(d_ev.alloc((size_t)n * SRT_ROW));
+  HIP_OK(d_meta.alloc((size_t)n * 4));
+  if ((rc = srt_crossings_device(nsurf, surfaces, nrays, d_off.p, d_rows.p, d_ev.p, d_meta.p, n, d_count.p, nullptr))) return rc;
+  HIP_OK(hipDeviceSynchronize());
+  double *er = (double *)malloc((size_t)n * SRT_ROW * sizeof(double));
+  int32_t *em = (int32_t *)malloc((size_t)n * 4 * sizeof(int32_t));
+  hipError_t e = er && em ? hipMemcpy(er, d_ev.p, (size_t)n * SRT_ROW * sizeof(double), hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemcpy(em, d_meta.p, (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    free(er);
+    free(em);
+    return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "srt_crossings: %lld events: %s", (long long)n, hipGetErrorString(e));
+  }
+  *nevents = n;
+  *event_rows = er;
+  *event_meta = em;
   return SRT_OK;
 }
 

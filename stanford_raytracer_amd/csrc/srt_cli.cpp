@@ -210,7 +210,12 @@ int main(int argc, char **argv) {
          "           of the model of --modelnum at every node; an axis may have one node; --mag_coords=1 with model 6 or 7: the\n"
          "           grid is in MAG coordinates)\n"
          "           --damping_out=<file>: hot-plasma damping along the kept rows (raynum, row, t, rate, magnitude, flag);\n"
-         "           with --damping_in=<.ray file> instead of tracing: along the records of an existing file");
+         "           with --damping_in=<.ray file> instead of tracing: along the records of an existing file\n"
+         "           --crossings_in=<.ray file> --crossings_surfaces=<file> --crossings_out=<file> [--device=N]: where and when the\n"
+         "           rays of an existing file cross surfaces, located on the cubic Hermite curve through consecutive records;\n"
+         "           the surfaces file holds one `kind p0 p1 p2 p3` per line (0 sphere: radius in m; 1 L-shell: L; 2 magnetic\n"
+         "           latitude: radians; 3 plane: normal and offset; trailing values may be absent); one record per crossing:\n"
+         "           raynum, surface, interval, direction (4 i10), then t, pos, vprel, vgrel, n, B0, Ns (20 es24.15e3)");
     return 0;
   }
   {
@@ -420,6 +425,102 @@ int main(int argc, char **argv) {
       fclose(f);
       printf(" %lld rays, %lld records\n", (long long)n, (long long)nrec);
       srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed);
+      return 0;
+    }
+  }
+  {
+    // ours: --crossings_in=<existing .ray file> --crossings_surfaces=<file> --crossings_out=<file>: where and when the rays of a
+    // file this program or the reference's driver wrote cross the surfaces of the second file (include/srt.h), without tracing
+    std::string cin_path, csurf, cout_path;
+    const bool have_in = getopt_named("crossings_in", cin_path), have_surf = getopt_named("crossings_surfaces", csurf),
+               have_out = getopt_named("crossings_out", cout_path);
+    if (have_in || have_surf || have_out) {
+      need(have_in, "crossings_in");
+      need(have_surf, "crossings_surfaces");
+      need(have_out, "crossings_out");
+      int device = 0;
+      get_int("device", device);
+      // one surface per line, list-directed: kind p0 p1 p2 p3; trailing values may be absent (0); a real kind is floored
+      std::vector<srt_surface> surf;
+      {
+        FILE *sf = fopen(csurf.c_str(), "r");
+        if (!sf) {
+          fprintf(stderr, "raytracer: --crossings_surfaces: cannot open %s\n", csurf.c_str());
+          return 1;
+        }
+        char line[1024];
+        int lineno = 0;
+        while (fgets(line, sizeof line, sf)) {
+          ++lineno;
+          double v[5] = {0, 0, 0, 0, 0};
+          int nv = 0;
+          for (char *q = line; *q; ++q)
+            if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
+            else if (*q == 'd' || *q == 'D') *q = 'e';
+          char *q = line;
+          bool bad = false;
+          for (;;) {
+            while (*q == ' ') ++q;
+            if (!*q) break;
+            char *end = nullptr;
+            const double x = strtod(q, &end);
+            if (end == q || nv == 5) {
+              bad = true;
+              break;
+            }
+            v[nv++] = x;
+            q = end;
+          }
+          if (bad) {
+            fclose(sf);
+            fprintf(stderr, "raytracer: --crossings_surfaces: %s, line %d: expected `kind p0 p1 p2 p3` (at most five numbers)\n", csurf.c_str(), lineno);
+            return 1;
+          }
+          if (nv == 0) continue; // an empty line
+          srt_surface s;
+          memset(&s, 0, sizeof s);
+          s.kind = (int32_t)floor(v[0]);
+          for (int k = 0; k < 4; ++k) s.p[k] = v[1 + k];
+          surf.push_back(s);
+        }
+        fclose(sf);
+        if (surf.empty() || surf.size() > SRT_MAXSURF) {
+          fprintf(stderr, "raytracer: --crossings_surfaces: %s holds %zu surfaces (1 .. %d are taken)\n", csurf.c_str(), surf.size(), SRT_MAXSURF);
+          return 1;
+        }
+      }
+      int32_t nspec = 0;
+      double qs[4], ms[4], *w0 = nullptr, *packed = nullptr;
+      int64_t nrec = 0, *raynum = nullptr;
+      int32_t *stop = nullptr, *kept = nullptr;
+      const int64_t n = srt_read_ray_file(cin_path.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &packed);
+      if (n < 0) {
+        fprintf(stderr, "raytracer: --crossings_in: %s\n", srt_last_error());
+        return 1;
+      }
+      std::vector<int64_t> offsets((size_t)n + 1, 0);
+      for (int64_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + kept[i];
+      int64_t nev = 0;
+      double *ev = nullptr;
+      int32_t *meta = nullptr;
+      if (nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
+        CHECK(srt_init(device));
+        CHECK(srt_crossings((int)surf.size(), surf.data(), n, offsets.data(), packed, &nev, &ev, &meta));
+      } else {
+        // the surfaces are still looked at: a bad one is refused whatever the file holds
+        int64_t zero[1] = {0};
+        const int rc = srt_crossings((int)surf.size(), surf.data(), 0, zero, nullptr, &nev, &ev, &meta);
+        if (rc == SRT_EINVAL) {
+          fprintf(stderr, "raytracer: %s\n", srt_last_error());
+          return 1;
+        }
+        nev = 0;
+      }
+      std::vector<int64_t> evray((size_t)nev);
+      for (int64_t e = 0; e < nev; ++e) evray[e] = raynum[meta[4 * e]];
+      CHECK(srt_crossings_file_write(cout_path.c_str(), nev, evray.data(), meta, ev));
+      printf(" %lld rays, %lld records, %zu surfaces, %lld crossings\n", (long long)n, (long long)nrec, surf.size(), (long long)nev);
+      srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed), srt_free(ev), srt_free(meta);
       return 0;
     }
   }

@@ -851,6 +851,35 @@ extern "C" int srt_write_ray_file_packed(const char *path, int append, int64_t r
   return write_ray_records(path, append, raynum0, nrays, nspec, qs, ms, w0, rows, stopcond, prefix, 0, 1);
 }
 
+// ---- crossings file: one record per event, (4 i10, 20 es24.15e3): raynum, surface + 1, interval + 1, direction, the row ----
+extern "C" int srt_crossings_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
+                                        const double *event_rows) {
+  if (!path || nevents < 0 || (nevents > 0 && (!raynum || !event_meta || !event_rows)))
+    return srt_set_error(SRT_EINVAL, "srt_crossings_file_write: null argument");
+  for (int64_t e = 0; e < nevents; ++e)
+    if (raynum[e] < 0 || raynum[e] > 9999999999ll)
+      return srt_set_error(SRT_EINVAL, "srt_crossings_file_write: ray number %lld of event %lld does not fit the record's i10 field",
+                           (long long)raynum[e], (long long)e);
+  FILE *fp = fopen(path, "w");
+  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
+  std::vector<char> big(1 << 22);
+  setvbuf(fp, big.data(), _IOFBF, big.size());
+  const size_t L = 40 + (size_t)SRT_ROW * 24 + 1;
+  std::vector<char> rec(L + 8);
+  for (int64_t e = 0; e < nevents; ++e) {
+    const int32_t *m = event_meta + 4 * e;
+    char head[48];
+    snprintf(head, sizeof head, "%10lld%10d%10d%10d", (long long)raynum[e], (int)m[1] + 1, (int)m[2] + 1, (int)m[3]);
+    memcpy(rec.data(), head, 40);
+    char *q = rec.data() + 40;
+    for (int c = 0; c < SRT_ROW; ++c, q += 24) put_es24(event_rows[(size_t)e * SRT_ROW + c], q);
+    *q = '\n';
+    fwrite(rec.data(), 1, L, fp);
+  }
+  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
+  return SRT_OK;
+}
+
 // ---- frame rotation SM <-> MAG (xform_double's sm_to_mag_d / mag_to_sm_d; srt_xform.hpp) ----
 extern "C" int srt_sm_to_mag(int yearday, int msec, int inverse, int64_t n, const double *x, double *out) {
   if (inverse != 0 && inverse != 1) return srt_set_error(SRT_EINVAL, "srt_sm_to_mag: inverse = %d is neither 0 (SM -> MAG) nor 1 (MAG -> SM)", inverse);

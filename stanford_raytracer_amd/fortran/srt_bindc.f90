@@ -22,6 +22,12 @@ module srt_bindc
      integer(c_int32_t) :: m(8)
      real(c_double) :: Ne_h, kT, tol
   end type srt_damping_params
+  ! srt_surface of include/srt.h: kind 0 sphere, 1 dipole L-shell, 2 magnetic latitude (radians), 3 plane
+  integer(c_int), parameter :: SRT_MAXSURF = 16
+  type, bind(C) :: srt_surface
+     integer(c_int32_t) :: kind, reserved
+     real(c_double) :: p(4)
+  end type srt_surface
   ! srt_segment: what one srt_trace_run_next hands out (valid until the next call on the run).  c_f_pointer turns the members
   ! into arrays: ray(nrays), offsets(nrays+1), rows(20, offsets(nrays+1)), nrows(nrays), stopcond(nrays)
   type, bind(C) :: srt_segment
@@ -170,6 +176,38 @@ module srt_bindc
        real(c_double) :: rate(*), magnitude(*)
        integer(c_int32_t) :: flag(*)
      end function srt_damping
+     ! surface crossings along packed kept rows: offsets(nrays+1), rows(20, offsets(nrays+1)); event_rows and event_meta come
+     ! back as malloc'd C arrays (c_f_pointer to (20, nevents) and (4, nevents); srt_free)
+     integer(c_int) function srt_crossings(nsurf, surfaces, nrays, offsets, rows, nevents, event_rows, event_meta) &
+          bind(C, name="srt_crossings")
+       import :: c_int, c_int64_t, c_double, c_ptr, srt_surface
+       integer(c_int), value :: nsurf
+       type(srt_surface), intent(in) :: surfaces(*)
+       integer(c_int64_t), value :: nrays
+       integer(c_int64_t), intent(in) :: offsets(*)
+       real(c_double), intent(in) :: rows(*)
+       integer(c_int64_t) :: nevents
+       type(c_ptr) :: event_rows, event_meta
+     end function srt_crossings
+     ! the same on device buffers (all type(c_ptr), value, but the host array `surfaces`); asynchronous on `stream`
+     integer(c_int) function srt_crossings_device(nsurf, surfaces, nrays, d_offsets, d_rows, d_event_rows, d_event_meta, &
+          capacity, d_count, stream) bind(C, name="srt_crossings_device")
+       import :: c_int, c_int64_t, c_ptr, srt_surface
+       integer(c_int), value :: nsurf
+       type(srt_surface), intent(in) :: surfaces(*)
+       integer(c_int64_t), value :: nrays, capacity
+       type(c_ptr), value :: d_offsets, d_rows, d_event_rows, d_event_meta, d_count, stream
+     end function srt_crossings_device
+     ! one (4 i10, 20 es24.15e3) record per event: raynum(nevents), event_meta(4, nevents), event_rows(20, nevents)
+     integer(c_int) function srt_crossings_file_write(path, nevents, raynum, event_meta, event_rows) &
+          bind(C, name="srt_crossings_file_write")
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_char
+       character(kind=c_char), dimension(*) :: path
+       integer(c_int64_t), value :: nevents
+       integer(c_int64_t), intent(in) :: raynum(*)
+       integer(c_int32_t), intent(in) :: event_meta(*)
+       real(c_double), intent(in) :: event_rows(*)
+     end function srt_crossings_file_write
      integer(c_int) function srt_model_nspec(model) bind(C, name="srt_model_nspec")
        import :: c_int, c_ptr
        type(c_ptr), value :: model

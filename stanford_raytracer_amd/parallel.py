@@ -90,6 +90,38 @@ def pack_rows_device(rows, nrows, outputper, stream=None, slot=None):
     return packed, offsets
 
 
+def crossings_device(packed, offsets, surfaces, capacity=None, stream=None):
+    """srt_crossings_device on torch CUDA tensors (packed[>= offsets[n], 20], offsets[n + 1] as pack_rows_device returns them)
+    -> (event_rows[capacity, 20], meta[capacity, 4] int32, count[1] int64), all on the device; the first min(count, capacity)
+    events are valid.  capacity=None: a count-only call first, then room for exactly the events there are (one wait for the
+    GPU); capacity=0: count only, event_rows and meta are None."""
+    import ctypes as C
+
+    import torch
+
+    from . import api
+
+    arr, ns = api.surface_array(surfaces)
+    n = offsets.shape[0] - 1
+    dev = offsets.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if capacity is None:
+        api._check(api.lib().srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), None, None, 0,
+                                                  count.data_ptr(), st.cuda_stream))
+        st.synchronize()
+        capacity = int(count.item())
+    if capacity == 0:
+        api._check(api.lib().srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), None, None, 0,
+                                                  count.data_ptr(), st.cuda_stream))
+        return None, None, count
+    ev = torch.zeros((capacity, ROW), dtype=torch.float64, device=dev)
+    meta = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
+    api._check(api.lib().srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), ev.data_ptr(), meta.data_ptr(),
+                                              C.c_int64(capacity), count.data_ptr(), st.cuda_stream))
+    return ev, meta, count
+
+
 def _sync(t):
     if t.is_cuda:
         import torch
