@@ -471,6 +471,79 @@ int srt_crossings(int nsurf, const srt_surface *surfaces, int64_t nrays, const i
 int srt_crossings_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
                              const double *event_rows);
 
+/* ---- traced rays binned onto a grid: dwell time and power maps ----
+ * No piece of the reference does this either (matlab/ only plots); it is what a million rays are traced for: how much ray
+ * time, or damped wave power, lies in each cell of an (L, magnetic latitude) meridian grid, an (x, z) plane or an (r, latitude,
+ * MLT) volume -- on the device, instead of a host loop over the rows.
+ * INPUT: the PACKED layout of the crossings above, offsets[nrays + 1] and rows[offsets[nrays]][SRT_ROW], and two optional
+ * weights: rowweight[offsets[nrays]], one per packed row (e.g. the square of srt_damping's magnitude), and rayweight[nrays]
+ * (e.g. a source spectrum).  A NULL weight means 1.
+ * SUB-SAMPLES: the interval (j, j + 1) of two consecutive kept rows of one ray is USABLE exactly when the crossings' rule says
+ * so (t, pos, vgrel finite at both ends, t_{j+1} != t_j) and w_j, w_{j+1} and the ray's weight are finite.  A usable interval
+ * is cut into nsub equal pieces of sigma (1 <= nsub <= 64); piece k = 0 .. nsub - 1 is one SAMPLE at sigma = (k + 1/2) / nsub,
+ * at the position p(sigma) on the crossings' cubic Hermite curve, with the weight W = rayweight (w_j + sigma (w_{j+1} - w_j))
+ * and the DEPOSIT d = W (h / nsub) seconds, h = t_{j+1} - t_j.
+ * COORDINATES: the grid has 1 .. 3 axes; an axis is a coordinate function of x (SM metres, R_E = 6371.2e3) and n >= 1 cells
+ * given by n + 1 strictly increasing finite edges; cell i holds edges[i] <= c < edges[i + 1].
+ *   kind 0, 1, 2   x, y, z
+ *   kind 3         r = |x|
+ *   kind 4         rho = sqrt(x^2 + y^2)
+ *   kind 5         dipole L = r^3 / (R_E rho^2)
+ *   kind 6         s = z / r, the sine of the magnetic latitude (edges within [-1, 1])
+ *   kind 7         MLT in hours = mod(24 phi / 2 pi + 12, 24), phi = atan2(y, x), as ngo_3d_dens_model_adapter takes it
+ *                  (edges within [0, 24])
+ * Kinds 0 .. 6 use only +, *, / and sqrt, products not fused into sums.
+ * CELL INDEX: a sample with any coordinate outside its axis, or not finite (rho = 0 for L, r = 0 for s), is OUTSIDE and deposits
+ * nothing.  The cell index is (i2 n1 + i1) n0 + i0.
+ * ACCUMULATION: ticks[cell] += llrint(d / quantum), rounded to nearest even; quantum > 0 is finite (2^-30 s is a good default),
+ * the accumulator is int64.  hits[cell] += 1.  An interval whose |d / quantum| >= 2^62 (or is not a number) at ANY of its
+ * samples is skipped whole.
+ * counters[4], int64: intervals used, intervals skipped (not usable, or a deposit too large), samples deposited, samples
+ * outside.  deposited + outside = nsub * used; the sum of hits = deposited; used + skipped = the sum over rays of (rows - 1).
+ * Cells hold INTEGERS so that the map is the same from run to run, from a host build and the device, for any launch geometry and
+ * for any split of the rays over calls, segments or GPUs (int64 maps add exactly).  What follows from that:
+ *   - a cell's sum wraps beyond 2^63 ticks: the caller chooses quantum accordingly (2^-30 s leaves 8.6e9 weighted seconds);
+ *   - each deposit is rounded by at most quantum / 2;
+ *   - as with crossings, what the kept rows do not show is not seen: the curve between two rows is the Hermite cubic, a sample
+ *     is a point, and a piece that straddles a cell boundary goes whole to the cell of its midpoint.
+ * SRT_EINVAL, by name, before a device is looked at: naxes outside 1 .. 3, nsub outside 1 .. 64, an unknown kind, n < 1 or
+ * > 1024, NULL, non-finite or non-increasing edges, a kind-6 edge outside [-1, 1], a kind-7 edge outside [0, 24], a non-finite
+ * or non-positive quantum, more than 2^31 - 1 cells, both outputs NULL, host offsets that decrease or do not start at 0. */
+typedef struct srt_bin_axis {
+  int32_t kind;
+  int32_t n;
+  const double *edges; /* host memory, n + 1 values */
+} srt_bin_axis;
+typedef struct srt_bin_params {
+  int32_t naxes;
+  int32_t nsub;
+  double quantum;
+  srt_bin_axis axis[3];
+} srt_bin_params;
+/* On buffers resident in device memory (`params` and its edges are host memory).  The call ACCUMULATES into d_ticks[ncells],
+ * d_hits[ncells] (int64; either may be NULL, not both) and d_counters[4], which the caller zeroes: calls over shards, segments
+ * or launch sets add up exactly.  The interval between the last row of one segment and the first of the next belongs to
+ * neither packed set and is not binned (a carry across segments is the caller's).  The device is found from the buffers; the
+ * call reads d_offsets[nrays] (8 bytes) behind the work already on `stream`, checks it against the allocation d_rows points
+ * into, takes its scratch from hipMallocAsync, and from there on is asynchronous on `stream`.  Grids of up to 4096 cells are
+ * accumulated in a block-private copy in LDS first, larger ones straight in device memory; the integers are the same. */
+int srt_bin_rays_device(const srt_bin_params *params, int64_t nrays, const int64_t *d_offsets, const double *d_rows,
+                        const double *d_rowweight, const double *d_rayweight, int64_t *d_ticks, int64_t *d_hits,
+                        int64_t *d_counters, void *stream);
+/* The same on host buffers: zeroes, runs, and returns malloc'd *ticks[ncells] and *hits[ncells] (srt_free; either pointer
+ * argument may be NULL, not both) and counters[4]. */
+int srt_bin_rays(const srt_bin_params *params, int64_t nrays, const int64_t *offsets, const double *rows, const double *rowweight,
+                 const double *rayweight, int64_t **ticks, int64_t **hits, int64_t counters[4]);
+/* The number of cells of a grid; validates `params` as the calls above do.  Host only. */
+int srt_bin_cells(const srt_bin_params *params, int64_t *ncells);
+/* A map as text.  Line 1: naxes, nsub (2 i10), quantum (es24.15e3).  Per axis two lines: kind, n (2 i10); its n + 1 edges
+ * (es24.15e3 each).  Then one record per cell in index order: ticks * quantum (es24.15e3), hits (i20).  A NULL ticks or hits is
+ * written as zeros.  The reader returns the grid (params->axis[a].edges point into the malloc'd *edges), *ncells and malloc'd
+ * *sum[ncells] = ticks * quantum as the file keeps it and *hits[ncells] (srt_free all three), and refuses (SRT_EIO) a file that
+ * is cut short or holds more than its header announces.  Pure host code, needs no GPU. */
+int srt_bin_file_write(const char *path, const srt_bin_params *params, const int64_t *ticks, const int64_t *hits);
+int srt_bin_file_read(const char *path, srt_bin_params *params, double **edges, int64_t *ncells, double **sum, int64_t **hits);
+
 /* ---- file formats of the boundary ---- */
 /* ray input file: 7 list-directed reals per line (raytracer_driver.f95:1146); returns count, fills
  * malloc'd arrays the caller frees with srt_free */

@@ -66,6 +66,16 @@ class Surface(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 4)]
 
 
+class BinAxis(C.Structure):
+    """srt_bin_axis of include/srt.h: a coordinate kind, n cells, n + 1 edges in host memory; see axis() and axis_maglat()."""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("edges", C.POINTER(C.c_double))]
+
+
+class BinParams(C.Structure):
+    """srt_bin_params of include/srt.h."""
+    _fields_ = [("naxes", C.c_int32), ("nsub", C.c_int32), ("quantum", C.c_double), ("axis", BinAxis * 3)]
+
+
 MAXSURF = 16  # SRT_MAXSURF
 RUNNING = -1  # SRT_RUNNING: stopcond of a paused ray
 STATE = 17    # SRT_STATE: doubles in a paused ray's record
@@ -179,6 +189,12 @@ def lib():
     L.srt_crossings_device.argtypes = [C.c_int, C.POINTER(Surface), C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp]
     L.srt_crossings.argtypes = [C.c_int, C.POINTER(Surface), C.c_int64, i64p, dp, i64p, C.POINTER(dp), C.POINTER(ip)]
     L.srt_crossings_file_write.argtypes = [C.c_char_p, C.c_int64, i64p, ip, dp]
+    bpp = C.POINTER(BinParams)
+    L.srt_bin_rays_device.argtypes = [bpp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.srt_bin_rays.argtypes = [bpp, C.c_int64, i64p, dp, dp, dp, C.POINTER(i64p), C.POINTER(i64p), i64p]
+    L.srt_bin_cells.argtypes = [bpp, i64p]
+    L.srt_bin_file_write.argtypes = [C.c_char_p, bpp, i64p, i64p]
+    L.srt_bin_file_read.argtypes = [C.c_char_p, bpp, C.POINTER(dp), i64p, C.POINTER(dp), C.POINTER(i64p)]
     _lib = L
     return L
 
@@ -754,6 +770,135 @@ def write_crossings_file(path, raynum, meta, event_rows):
         raise ValueError("raynum, meta and event_rows name %d, %d and %d events" % (len(raynum), len(meta), len(event_rows)))
     _check(lib().srt_crossings_file_write(os.fsencode(path), len(meta), raynum.ctypes.data_as(C.POINTER(C.c_int64)),
                                           meta.ctypes.data_as(ip), _dp(event_rows)))
+
+
+# ---- traced rays binned onto a grid: dwell time and power maps (include/srt.h) -------
+AXIS_KINDS = {"x": 0, "y": 1, "z": 2, "r": 3, "rho": 4, "L": 5, "sinlat": 6, "mlt": 7}
+
+
+def axis(kind_name, edges):
+    """An axis of a binning grid: kind_name of AXIS_KINDS (x y z r rho in metres, dipole L, sinlat = z / r, mlt in hours) and
+    its n + 1 increasing edges -> (kind, edges as float64)."""
+    if kind_name not in AXIS_KINDS:
+        raise ValueError("unknown axis kind %r (one of %s)" % (kind_name, " ".join(AXIS_KINDS)))
+    return AXIS_KINDS[kind_name], _f64(edges).reshape(-1).copy()
+
+
+def axis_maglat(edges_rad):
+    """An axis of magnetic latitude from edges in radians: the sines are taken here (monotone on [-pi/2, pi/2]), as maglat()
+    does for a surface."""
+    e = _f64(edges_rad).reshape(-1)
+    if not np.all(np.abs(e) <= np.pi / 2):
+        raise ValueError("latitude edges lie within -pi/2 .. pi/2 radians")
+    return AXIS_KINDS["sinlat"], np.sin(e)
+
+
+def bin_params(axes, nsub=8, quantum=2.0 ** -30):
+    """A sequence of axis() results -> BinParams (it keeps the edge arrays alive as ._edges)."""
+    axes = list(axes)
+    p = BinParams()
+    p.naxes, p.nsub, p.quantum = len(axes), int(nsub), float(quantum)
+    p._edges = []
+    for a, (kind, edges) in enumerate(axes[:3]):
+        e = _f64(edges).reshape(-1)
+        p._edges.append(e)
+        p.axis[a] = BinAxis(int(kind), e.size - 1, _dp(e))
+    return p
+
+
+def bin_shape(p):
+    """The numpy shape of a map of BinParams p: [n2][n1][n0] with absent axes dropped."""
+    return tuple(int(p.axis[a].n) for a in range(p.naxes))[::-1]
+
+
+def bin_cells(p):
+    n = C.c_int64()
+    _check(lib().srt_bin_cells(C.byref(p), C.byref(n)))
+    return n.value
+
+
+def bin_rays(offsets, rows, axes, nsub=8, quantum=2.0 ** -30, row_weight=None, ray_weight=None):
+    """The rays of a packed row set (offsets[n+1], rows[offsets[n], 20]) binned onto the grid of `axes` (axis(), axis_maglat()):
+    every interval of consecutive kept rows is cut into nsub pieces on the cubic Hermite curve, and each piece deposits its
+    weight x duration into the cell of its midpoint, in integer ticks of `quantum` seconds.  row_weight[offsets[n]] and
+    ray_weight[n] are optional.  -> dict(sum = ticks * quantum as float64, ticks, hits (int64), all shaped [n2][n1][n0] with
+    absent axes dropped, and counters[4] = intervals used, intervals skipped, samples deposited, samples outside)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    rows = _f64(rows).reshape(-1, ROW)
+    if offsets.ndim != 1 or offsets.size < 1:
+        raise ValueError("offsets holds nrays + 1 entries")
+    if rows.shape[0] < offsets[-1]:
+        raise ValueError("offsets name %d rows, rows holds %d" % (offsets[-1], rows.shape[0]))
+    n = offsets.size - 1
+    rw = yw = None
+    if row_weight is not None:
+        rw = _f64(row_weight).reshape(-1)
+        if rw.size < offsets[-1]:
+            raise ValueError("offsets name %d rows, row_weight holds %d" % (offsets[-1], rw.size))
+    if ray_weight is not None:
+        yw = _f64(ray_weight).reshape(-1)
+        if yw.size != n:
+            raise ValueError("ray_weight holds %d entries for %d rays" % (yw.size, n))
+    p = bin_params(axes, nsub, quantum)
+    i64p = C.POINTER(C.c_int64)
+    pt, ph = i64p(), i64p()
+    counters = np.zeros(4, dtype=np.int64)
+    _check(lib().srt_bin_rays(C.byref(p), n, offsets.ctypes.data_as(i64p), _dp(rows), _dp(rw) if rw is not None else None,
+                              _dp(yw) if yw is not None else None, C.byref(pt), C.byref(ph), counters.ctypes.data_as(i64p)))
+    try:
+        nc, shape = bin_cells(p), bin_shape(p)
+        ticks = np.ctypeslib.as_array(pt, (nc,)).copy().reshape(shape)
+        hits = np.ctypeslib.as_array(ph, (nc,)).copy().reshape(shape)
+    finally:
+        lib().srt_free(pt)
+        lib().srt_free(ph)
+    return {"sum": ticks.astype(np.float64) * float(quantum), "ticks": ticks, "hits": hits, "counters": counters}
+
+
+def bin_rays_padded(rows, nrows, outputper, axes, nsub=8, quantum=2.0 ** -30, row_weight_padded=None, ray_weight=None):
+    """bin_rays() of rows[n, slots, 20], nrows[n] as Model.trace returns them: packs first, and packs row_weight_padded[n, slots]
+    (e.g. the square of the magnitude damping() returns) with the rows."""
+    offsets, packed = pack_rows(rows, nrows, outputper)
+    rw = None
+    if row_weight_padded is not None:
+        w = _f64(row_weight_padded)
+        n, slots = w.shape
+        kept = np.diff(offsets)
+        rw = w[np.arange(slots)[None, :] < kept[:, None]]
+    return bin_rays(offsets, packed, axes, nsub, quantum, rw, ray_weight)
+
+
+def write_bin_file(path, axes, ticks, hits, nsub=8, quantum=2.0 ** -30):
+    """A map as text (include/srt.h): the grid, then per cell ticks * quantum (es24.15e3) and hits (i20)."""
+    p = bin_params(axes, nsub, quantum)
+    i64p = C.POINTER(C.c_int64)
+    t = None if ticks is None else np.ascontiguousarray(ticks, dtype=np.int64).reshape(-1)
+    h = None if hits is None else np.ascontiguousarray(hits, dtype=np.int64).reshape(-1)
+    nc = bin_cells(p)
+    for name, a in (("ticks", t), ("hits", h)):
+        if a is not None and a.size != nc:
+            raise ValueError("%s holds %d cells, the grid has %d" % (name, a.size, nc))
+    _check(lib().srt_bin_file_write(os.fsencode(path), C.byref(p), t.ctypes.data_as(i64p) if t is not None else None,
+                                    h.ctypes.data_as(i64p) if h is not None else None))
+
+
+def read_bin_file(path):
+    """-> dict(axes = [(kind, edges)], nsub, quantum, sum, hits), the maps shaped [n2][n1][n0] with absent axes dropped."""
+    p = BinParams()
+    i64p = C.POINTER(C.c_int64)
+    pe, ps, ph, nc = dp(), dp(), i64p(), C.c_int64()
+    _check(lib().srt_bin_file_read(os.fsencode(path), C.byref(p), C.byref(pe), C.byref(nc), C.byref(ps), C.byref(ph)))
+    try:
+        axes = [(int(p.axis[a].kind), np.ctypeslib.as_array(p.axis[a].edges, (p.axis[a].n + 1,)).copy()) for a in range(p.naxes)]
+        shape = bin_shape(p)
+        out = {"axes": axes, "nsub": int(p.nsub), "quantum": float(p.quantum),
+               "sum": np.ctypeslib.as_array(ps, (nc.value,)).copy().reshape(shape),
+               "hits": np.ctypeslib.as_array(ph, (nc.value,)).copy().reshape(shape)}
+    finally:
+        lib().srt_free(pe)
+        lib().srt_free(ps)
+        lib().srt_free(ph)
+    return out
 
 
 # ---- model-3 grid files: text of the reference's grid builder <-> binary side-format (host code, no GPU) -------

@@ -31,6 +31,7 @@
 #include "srt_damping.hpp"
 #include "srt_xform.hpp"
 #include "srt_crossings.hpp"
+#include "srt_binning.hpp"
 #include <hipcub/hipcub.hpp>
 
 using namespace srt;
@@ -2293,6 +2294,134 @@ extern "C" int srt_crossings(int nsurf, const srt_surface *surfaces, int64_t nra
   *nevents = n;
   *event_rows = er;
   *event_meta = em;
+  return SRT_OK;
+}
+
+// ---- traced rays binned onto a grid (kernel and point functions: srt_binning.hpp) ----
+extern "C" int srt_bin_cells(const srt_bin_params *params, int64_t *ncells) {
+  namespace bn = srt::binning;
+  bn::Grid G;
+  std::vector<double> edges(3 * (bn::MAXN + 1));
+  char why[200];
+  if (bn::prepare(params, &G, edges.data(), why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_bin_cells: %s", why);
+  if (!ncells) return srt_set_error(SRT_EINVAL, "srt_bin_cells: null ncells");
+  *ncells = G.ncells;
+  return SRT_OK;
+}
+
+extern "C" int srt_bin_rays_device(const srt_bin_params *params, int64_t nrays, const int64_t *d_offsets, const double *d_rows,
+                                   const double *d_rowweight, const double *d_rayweight, int64_t *d_ticks, int64_t *d_hits,
+                                   int64_t *d_counters, void *stream) {
+  namespace bn = srt::binning;
+  bn::Grid G;
+  std::vector<double> edges(3 * (bn::MAXN + 1));
+  char why[200];
+  if (bn::prepare(params, &G, edges.data(), why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: %s", why);
+  if (!d_ticks && !d_hits) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: both outputs (d_ticks and d_hits) are null");
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: nrays = %lld is negative", (long long)nrays);
+  if (!d_offsets || !d_counters) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: null d_offsets or d_counters");
+  int dev = -1, rc;
+  {
+    const void *ptrs[7] = {d_offsets, d_counters, d_rows, d_rowweight, d_rayweight, d_ticks, d_hits};
+    if ((rc = device_of("srt_bin_rays_device", ptrs, 7, &dev))) return rc;
+  }
+  DeviceScope scope;
+  if ((rc = scope.enter(dev))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!within_allocation(d_offsets, ((size_t)nrays + 1) * sizeof(int64_t)))
+    return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: d_offsets has no room for nrays + 1 = %lld entries", (long long)nrays + 1);
+  if (!within_allocation(d_counters, 4 * sizeof(int64_t)) || (d_ticks && !within_allocation(d_ticks, (size_t)G.ncells * sizeof(int64_t))) ||
+      (d_hits && !within_allocation(d_hits, (size_t)G.ncells * sizeof(int64_t))))
+    return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: an output has no room for %lld cells (or d_counters for 4 counters)", G.ncells);
+  if (d_rayweight && !within_allocation(d_rayweight, (size_t)nrays * sizeof(double)))
+    return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: d_rayweight has no room for nrays = %lld entries", (long long)nrays);
+  // the edges go up in front of the one thing the host has to know, how many rows there are: one wait covers both, and the
+  // host copy of the edges is done with when the wait returns
+  double *d_edges = nullptr;
+  HIP_OK(hipMallocAsync((void **)&d_edges, (size_t)G.nedges * sizeof(double), st));
+  long long total = 0;
+  hipError_t e = hipMemcpyAsync(d_edges, edges.data(), (size_t)G.nedges * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  const char *refuse = nullptr;
+  if (e == hipSuccess) {
+    if (total < 0) refuse = "is negative";
+    else if (total >= (1ll << 31) - 1) refuse = "rows are too many for one call (2^31 - 2 at most)";
+    else if (total >= 2 && !d_rows) refuse = "rows, and d_rows is null";
+    else if (total >= 2 && !within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double))) refuse = "rows, more than the allocation of d_rows holds";
+    else if (total >= 2 && d_rowweight && !within_allocation(d_rowweight, (size_t)total * sizeof(double))) refuse = "rows, more than the allocation of d_rowweight holds";
+  }
+  if (e == hipSuccess && !refuse && total >= 2) {
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned long long) == sizeof(int64_t), "int64");
+    const unsigned blocks = bn::launch_blocks(G, total);
+    const size_t lds = bn::lds_bytes(G);
+    if (G.ncells <= bn::LDS_CELLS)
+      hipLaunchKernelGGL(bn::bin_kernel<true>, dim3(blocks), dim3(bn::BLOCK), lds, st, G, (const double *)d_edges, (long long)nrays,
+                         (const long long *)d_offsets, total, d_rows, d_rowweight, d_rayweight, (unsigned long long *)d_ticks,
+                         (unsigned long long *)d_hits, (unsigned long long *)d_counters);
+    else
+      hipLaunchKernelGGL(bn::bin_kernel<false>, dim3(blocks), dim3(bn::BLOCK), lds, st, G, (const double *)d_edges, (long long)nrays,
+                         (const long long *)d_offsets, total, d_rows, d_rowweight, d_rayweight, (unsigned long long *)d_ticks,
+                         (unsigned long long *)d_hits, (unsigned long long *)d_counters);
+    e = hipGetLastError();
+  }
+  (void)hipFreeAsync(d_edges, st); // (also on the error path)
+  HIP_OK(e);
+  if (refuse) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: offsets[nrays] = %lld %s", total, refuse);
+  return SRT_OK;
+}
+
+extern "C" int srt_bin_rays(const srt_bin_params *params, int64_t nrays, const int64_t *offsets, const double *rows,
+                            const double *rowweight, const double *rayweight, int64_t **ticks, int64_t **hits, int64_t counters[4]) {
+  namespace bn = srt::binning;
+  bn::Grid G;
+  {
+    std::vector<double> edges(3 * (bn::MAXN + 1));
+    char why[200];
+    if (bn::prepare(params, &G, edges.data(), why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_bin_rays: %s", why);
+  }
+  if (!ticks && !hits) return srt_set_error(SRT_EINVAL, "srt_bin_rays: both outputs (ticks and hits) are null");
+  if (ticks) *ticks = nullptr;
+  if (hits) *hits = nullptr;
+  if (!counters) return srt_set_error(SRT_EINVAL, "srt_bin_rays: null counters");
+  for (int k = 0; k < 4; ++k) counters[k] = 0;
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_bin_rays: nrays = %lld is negative", (long long)nrays);
+  if (!offsets) return srt_set_error(SRT_EINVAL, "srt_bin_rays: null offsets");
+  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_bin_rays: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
+  for (int64_t r = 0; r < nrays; ++r)
+    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_bin_rays: offsets decrease at ray %lld", (long long)r);
+  const int64_t total = offsets[nrays];
+  if (total > 0 && !rows) return srt_set_error(SRT_EINVAL, "srt_bin_rays: null rows");
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  const size_t nc = (size_t)G.ncells;
+  DevBuf<double> d_rows, d_roww, d_rayw;
+  DevBuf<int64_t> d_off, d_out; // d_out: counters[4], ticks[nc], hits[nc]
+  HIP_OK(d_out.alloc(4 + 2 * nc));
+  HIP_OK(hipMemset(d_out.p, 0, (4 + 2 * nc) * sizeof(int64_t)));
+  if (total >= 2) {
+    if ((rc = upload(d_rows, rows, (size_t)total * SRT_ROW))) return rc;
+    if (rowweight && (rc = upload(d_roww, rowweight, (size_t)total))) return rc;
+    if (rayweight && (rc = upload(d_rayw, rayweight, (size_t)nrays))) return rc;
+    HIP_OK(d_off.alloc((size_t)nrays + 1));
+    HIP_OK(hipMemcpy(d_off.p, offsets, ((size_t)nrays + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if ((rc = srt_bin_rays_device(params, nrays, d_off.p, d_rows.p, rowweight ? d_roww.p : nullptr, rayweight ? d_rayw.p : nullptr,
+                                  ticks ? d_out.p + 4 : nullptr, hits ? d_out.p + 4 + nc : nullptr, d_out.p, nullptr)))
+      return rc;
+    HIP_OK(hipDeviceSynchronize());
+  }
+  int64_t *ht = ticks ? (int64_t *)malloc(nc * sizeof(int64_t)) : nullptr, *hh = hits ? (int64_t *)malloc(nc * sizeof(int64_t)) : nullptr;
+  hipError_t e = (ticks && !ht) || (hits && !hh) ? hipErrorOutOfMemory : hipMemcpy(counters, d_out.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && ht) e = hipMemcpy(ht, d_out.p + 4, nc * sizeof(int64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && hh) e = hipMemcpy(hh, d_out.p + 4 + nc, nc * sizeof(int64_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    free(ht);
+    free(hh);
+    return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "srt_bin_rays: %zu cells: %s", nc, hipGetErrorString(e));
+  }
+  if (ticks) *ticks = ht;
+  if (hits) *hits = hh;
   return SRT_OK;
 }
 

@@ -215,7 +215,13 @@ int main(int argc, char **argv) {
          "           rays of an existing file cross surfaces, located on the cubic Hermite curve through consecutive records;\n"
          "           the surfaces file holds one `kind p0 p1 p2 p3` per line (0 sphere: radius in m; 1 L-shell: L; 2 magnetic\n"
          "           latitude: radians; 3 plane: normal and offset; trailing values may be absent); one record per crossing:\n"
-         "           raynum, surface, interval, direction (4 i10), then t, pos, vprel, vgrel, n, B0, Ns (20 es24.15e3)");
+         "           raynum, surface, interval, direction (4 i10), then t, pos, vprel, vgrel, n, B0, Ns (20 es24.15e3)\n"
+         "           --bin_in=<.ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=9.313225746154785e-10]\n"
+         "           [--device=N]: the dwell-time map of the rays of an existing file: every interval of consecutive records is cut\n"
+         "           into bin_nsub pieces on the cubic Hermite curve, each deposits its duration into the cell of its midpoint, in\n"
+         "           whole ticks of bin_quantum seconds; the axes file holds one axis per line, `kind n e0 e1 .. en` (kind 0 .. 7\n"
+         "           or x y z r rho L sinlat mlt; metres, L, sine of the magnetic latitude, hours; 1 .. 3 axes of 1 .. 1024 cells);\n"
+         "           the output holds the grid, then per cell seconds (es24.15e3) and samples (i20)");
     return 0;
   }
   {
@@ -521,6 +527,120 @@ int main(int argc, char **argv) {
       CHECK(srt_crossings_file_write(cout_path.c_str(), nev, evray.data(), meta, ev));
       printf(" %lld rays, %lld records, %zu surfaces, %lld crossings\n", (long long)n, (long long)nrec, surf.size(), (long long)nev);
       srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed), srt_free(ev), srt_free(meta);
+      return 0;
+    }
+  }
+  {
+    // ours: --bin_in=<existing .ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=2^-30]: the dwell-time
+    // map of the rays of a file this program or the reference's driver wrote on the grid of the second file (include/srt.h),
+    // without tracing.  What is wrong with the flags or the files is refused by name with exit code 2.
+    std::string bin_path, baxes, bout_path;
+    const bool have_in = getopt_named("bin_in", bin_path), have_axes = getopt_named("bin_axes", baxes),
+               have_out = getopt_named("bin_out", bout_path);
+    if (have_in || have_axes || have_out) {
+      need(have_in, "bin_in");
+      need(have_axes, "bin_axes");
+      need(have_out, "bin_out");
+      int device = 0;
+      get_int("device", device);
+      srt_bin_params bp;
+      memset(&bp, 0, sizeof bp);
+      bp.nsub = 8;
+      bp.quantum = 9.313225746154785e-10; // 2^-30 s
+      get_int("bin_nsub", bp.nsub);
+      get_real("bin_quantum", bp.quantum);
+      // one axis per line: kind n e0 e1 .. en; the kind a number or a name; commas and d exponents are tolerated
+      std::vector<std::vector<double>> edges;
+      {
+        FILE *af = fopen(baxes.c_str(), "r");
+        if (!af) {
+          fprintf(stderr, "raytracer: --bin_axes: cannot open %s\n", baxes.c_str());
+          return 2;
+        }
+        static const char *names[8] = {"x", "y", "z", "r", "rho", "L", "sinlat", "mlt"};
+        std::vector<char> line(1 << 16);
+        int lineno = 0;
+        while (fgets(line.data(), (int)line.size(), af)) {
+          ++lineno;
+          for (char *q = line.data(); *q; ++q)
+            if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
+          char *q = line.data();
+          while (*q == ' ') ++q;
+          if (!*q) continue; // an empty line
+          const char *what = nullptr;
+          int kind = -1;
+          char *end = q;
+          while (*end && *end != ' ') ++end;
+          const std::string word(q, end);
+          for (int k = 0; k < 8; ++k)
+            if (word == names[k]) kind = k;
+          if (kind < 0) {
+            char *e2 = nullptr;
+            const double v = strtod(q, &e2);
+            if (e2 != end || !(v >= -1e9 && v <= 1e9)) what = "the kind is neither a number nor one of x y z r rho L sinlat mlt";
+            else kind = (int)floor(v);
+          }
+          std::vector<double> v;
+          for (q = end; !what;) {
+            while (*q == ' ') ++q;
+            if (!*q) break;
+            for (char *s = q; *s && *s != ' '; ++s)
+              if (*s == 'd' || *s == 'D') *s = 'e';
+            char *e2 = nullptr;
+            const double x = strtod(q, &e2);
+            if (e2 == q || (*e2 && *e2 != ' ')) what = "not a number";
+            v.push_back(x);
+            q = e2;
+          }
+          if (!what && (v.empty() || v[0] != floor(v[0]) || !(v[0] >= 1.0 && v[0] <= 1024.0))) what = "n is not a whole number of 1 .. 1024";
+          if (!what && v.size() != (size_t)v[0] + 2) what = "the line does not hold n + 1 edges";
+          if (!what && edges.size() == 3) what = "a fourth axis";
+          if (what) {
+            fclose(af);
+            fprintf(stderr, "raytracer: --bin_axes: %s, line %d: %s (expected `kind n e0 e1 .. en`)\n", baxes.c_str(), lineno, what);
+            return 2;
+          }
+          bp.axis[edges.size()].kind = kind;
+          bp.axis[edges.size()].n = (int32_t)v[0];
+          edges.emplace_back(v.begin() + 1, v.end());
+        }
+        fclose(af);
+        if (edges.empty()) {
+          fprintf(stderr, "raytracer: --bin_axes: %s holds no axis (1 .. 3 are taken)\n", baxes.c_str());
+          return 2;
+        }
+        bp.naxes = (int32_t)edges.size();
+        for (size_t a = 0; a < edges.size(); ++a) bp.axis[a].edges = edges[a].data();
+      }
+      int64_t ncells = 0;
+      if (srt_bin_cells(&bp, &ncells) != SRT_OK) { // --bin_nsub, --bin_quantum and the edges, by name
+        fprintf(stderr, "raytracer: --bin_axes / --bin_nsub / --bin_quantum: %s\n", srt_last_error());
+        return 2;
+      }
+      int32_t nspec = 0;
+      double qs[4], ms[4], *w0 = nullptr, *packed = nullptr;
+      int64_t nrec = 0, *raynum = nullptr;
+      int32_t *stop = nullptr, *kept = nullptr;
+      const int64_t n = srt_read_ray_file(bin_path.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &packed);
+      if (n < 0) {
+        fprintf(stderr, "raytracer: --bin_in: %s\n", srt_last_error());
+        return 2;
+      }
+      std::vector<int64_t> offsets((size_t)n + 1, 0);
+      for (int64_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + kept[i];
+      int64_t *ticks = nullptr, *hits = nullptr, counters[4] = {0, 0, 0, 0};
+      std::vector<int64_t> zeros;
+      if (nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
+        CHECK(srt_init(device));
+        CHECK(srt_bin_rays(&bp, n, offsets.data(), packed, nullptr, nullptr, &ticks, &hits, counters));
+      } else {
+        zeros.assign((size_t)ncells, 0);
+      }
+      CHECK(srt_bin_file_write(bout_path.c_str(), &bp, ticks ? ticks : zeros.data(), hits ? hits : zeros.data()));
+      printf(" %lld rays, %lld records, %lld cells: %lld intervals used, %lld skipped, %lld samples deposited, %lld outside\n",
+             (long long)n, (long long)nrec, (long long)ncells, (long long)counters[0], (long long)counters[1], (long long)counters[2],
+             (long long)counters[3]);
+      srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed), srt_free(ticks), srt_free(hits);
       return 0;
     }
   }

@@ -8,6 +8,9 @@
 
 #include "srt_host.hpp"
 #include "srt_xform.hpp"
+#define SRT_CROSSINGS_NO_KERNELS
+#define SRT_BINNING_NO_KERNELS
+#include "srt_binning.hpp"
 
 #include <charconv>
 #include <cerrno>
@@ -877,6 +880,108 @@ extern "C" int srt_crossings_file_write(const char *path, int64_t nevents, const
     fwrite(rec.data(), 1, L, fp);
   }
   if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
+  return SRT_OK;
+}
+
+// ---- bin file: a map of srt_bin_rays as text (include/srt.h) ----
+// the grid's soundness is srt_binning.hpp's prepare(), the host half of that header; -> 0 and *ncells, or -1 and `why`
+static int bin_file_cells(const srt_bin_params *params, int64_t *ncells, char *why, size_t whylen) {
+  srt::binning::Grid G;
+  std::vector<double> edges(3 * (srt::binning::MAXN + 1));
+  if (srt::binning::prepare(params, &G, edges.data(), why, whylen)) return -1;
+  *ncells = G.ncells;
+  return 0;
+}
+extern "C" int srt_bin_file_write(const char *path, const srt_bin_params *params, const int64_t *ticks, const int64_t *hits) {
+  if (!path) return srt_set_error(SRT_EINVAL, "srt_bin_file_write: null path");
+  int64_t ncells = 0;
+  char why[200];
+  if (bin_file_cells(params, &ncells, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_bin_file_write: %s", why);
+  FILE *fp = fopen(path, "w");
+  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
+  std::vector<char> big(1 << 22);
+  setvbuf(fp, big.data(), _IOFBF, big.size());
+  char num[25];
+  num[24] = 0;
+  put_es24(params->quantum, num);
+  fprintf(fp, "%10d%10d%s\n", (int)params->naxes, (int)params->nsub, num);
+  for (int a = 0; a < params->naxes; ++a) {
+    fprintf(fp, "%10d%10d\n", (int)params->axis[a].kind, (int)params->axis[a].n);
+    for (int i = 0; i <= params->axis[a].n; ++i) {
+      put_es24(params->axis[a].edges[i], num);
+      fwrite(num, 1, 24, fp);
+    }
+    fputc('\n', fp);
+  }
+  char rec[48];
+  for (int64_t c = 0; c < ncells; ++c) {
+    put_es24(ticks ? (double)ticks[c] * params->quantum : 0.0, rec);
+    snprintf(rec + 24, sizeof rec - 24, "%20lld\n", (long long)(hits ? hits[c] : 0));
+    fwrite(rec, 1, 45, fp);
+  }
+  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
+  return SRT_OK;
+}
+
+extern "C" int srt_bin_file_read(const char *path, srt_bin_params *params, double **edges, int64_t *ncells, double **sum, int64_t **hits) {
+  if (!path || !params || !edges || !ncells || !sum || !hits) return srt_set_error(SRT_EINVAL, "srt_bin_file_read: null argument");
+  *edges = nullptr, *sum = nullptr, *hits = nullptr, *ncells = 0;
+  std::vector<double> all;
+  std::string err;
+  if (!srt_host::read_all_numbers(path, all, err)) return srt_set_error(SRT_EIO, "%s: %s", path, err.c_str());
+  if (all.size() < 3 || !(all[0] >= 1.0 && all[0] <= 3.0) || all[0] != std::floor(all[0]) || all[1] != std::floor(all[1]) ||
+      !(all[1] >= 1.0 && all[1] <= 64.0))
+    return srt_set_error(SRT_EIO, "%s: bin file header (naxes nsub quantum) incomplete or out of range", path);
+  memset(params, 0, sizeof *params);
+  params->naxes = (int32_t)all[0];
+  params->nsub = (int32_t)all[1];
+  params->quantum = all[2];
+  size_t at = 3, eoff[3] = {0, 0, 0}, nedges = 0;
+  for (int a = 0; a < params->naxes; ++a) {
+    if (at + 2 > all.size() || all[at + 1] != std::floor(all[at + 1]) || !(all[at + 1] >= 1.0 && all[at + 1] <= 1024.0) ||
+        all[at] != std::floor(all[at]) || !(all[at] >= 0.0 && all[at] <= 7.0))
+      return srt_set_error(SRT_EIO, "%s: bin file: the header of axis %d (kind n) is cut short or out of range", path, a);
+    params->axis[a].kind = (int32_t)all[at];
+    params->axis[a].n = (int32_t)all[at + 1];
+    at += 2;
+    if (at + (size_t)params->axis[a].n + 1 > all.size())
+      return srt_set_error(SRT_EIO, "%s: bin file: the edges of axis %d are cut short", path, a);
+    eoff[a] = at;
+    at += (size_t)params->axis[a].n + 1;
+    nedges += (size_t)params->axis[a].n + 1;
+  }
+  double *ed = (double *)malloc(nedges * sizeof(double));
+  if (!ed) return srt_set_error(SRT_ENOMEM, "bin file of %zu edges", nedges);
+  size_t k = 0;
+  for (int a = 0; a < params->naxes; ++a) {
+    params->axis[a].edges = ed + k;
+    for (int i = 0; i <= params->axis[a].n; ++i) ed[k++] = all[eoff[a] + i];
+  }
+  int64_t nc = 0;
+  char why[200];
+  if (bin_file_cells(params, &nc, why, sizeof why)) {
+    free(ed);
+    memset(params, 0, sizeof *params);
+    return srt_set_error(SRT_EIO, "%s: bin file: %s", path, why);
+  }
+  if ((double)(all.size() - at) != 2.0 * (double)nc) {
+    free(ed);
+    memset(params, 0, sizeof *params);
+    return srt_set_error(SRT_EIO, "%s: bin file holds %zu values after its axes, its header announces %lld cells of two", path,
+                         all.size() - at, (long long)nc);
+  }
+  double *sm = (double *)malloc((size_t)nc * sizeof(double));
+  int64_t *hh = (int64_t *)malloc((size_t)nc * sizeof(int64_t));
+  if (!sm || !hh) {
+    free(ed), free(sm), free(hh);
+    memset(params, 0, sizeof *params);
+    return srt_set_error(SRT_ENOMEM, "bin file of %lld cells", (long long)nc);
+  }
+  for (int64_t c = 0; c < nc; ++c) {
+    sm[c] = all[at + 2 * (size_t)c];
+    hh[c] = (int64_t)all[at + 2 * (size_t)c + 1];
+  }
+  *edges = ed, *ncells = nc, *sum = sm, *hits = hh;
   return SRT_OK;
 }
 

@@ -28,6 +28,16 @@ module srt_bindc
      integer(c_int32_t) :: kind, reserved
      real(c_double) :: p(4)
   end type srt_surface
+  ! srt_bin_axis / srt_bin_params of include/srt.h: kind 0 .. 7 = x y z r rho L sinlat mlt; edges = c_loc of n + 1 doubles
+  type, bind(C) :: srt_bin_axis
+     integer(c_int32_t) :: kind, n
+     type(c_ptr) :: edges
+  end type srt_bin_axis
+  type, bind(C) :: srt_bin_params
+     integer(c_int32_t) :: naxes, nsub
+     real(c_double) :: quantum
+     type(srt_bin_axis) :: axis(3)
+  end type srt_bin_params
   ! srt_segment: what one srt_trace_run_next hands out (valid until the next call on the run).  c_f_pointer turns the members
   ! into arrays: ray(nrays), offsets(nrays+1), rows(20, offsets(nrays+1)), nrows(nrays), stopcond(nrays)
   type, bind(C) :: srt_segment
@@ -208,6 +218,49 @@ module srt_bindc
        integer(c_int32_t), intent(in) :: event_meta(*)
        real(c_double), intent(in) :: event_rows(*)
      end function srt_crossings_file_write
+     ! traced rays binned onto a grid: offsets(nrays+1), rows(20, offsets(nrays+1)), rowweight(offsets(nrays+1)) and
+     ! rayweight(nrays) as type(c_ptr) (c_null_ptr = all ones; c_loc of a target array otherwise); ticks and hits come back as
+     ! malloc'd C arrays of ncells int64 (c_f_pointer; srt_free); counters(4) = used, skipped, deposited, outside
+     integer(c_int) function srt_bin_rays(params, nrays, offsets, rows, rowweight, rayweight, ticks, hits, counters) &
+          bind(C, name="srt_bin_rays")
+       import :: c_int, c_int64_t, c_double, c_ptr, srt_bin_params
+       type(srt_bin_params), intent(in) :: params
+       integer(c_int64_t), value :: nrays
+       integer(c_int64_t), intent(in) :: offsets(*)
+       real(c_double), intent(in) :: rows(*)
+       type(c_ptr), value :: rowweight, rayweight
+       type(c_ptr) :: ticks, hits
+       integer(c_int64_t) :: counters(4)
+     end function srt_bin_rays
+     ! the same on device buffers (all type(c_ptr), value); ACCUMULATES into d_ticks, d_hits and d_counters, which the caller
+     ! zeroes; asynchronous on `stream`
+     integer(c_int) function srt_bin_rays_device(params, nrays, d_offsets, d_rows, d_rowweight, d_rayweight, d_ticks, d_hits, &
+          d_counters, stream) bind(C, name="srt_bin_rays_device")
+       import :: c_int, c_int64_t, c_ptr, srt_bin_params
+       type(srt_bin_params), intent(in) :: params
+       integer(c_int64_t), value :: nrays
+       type(c_ptr), value :: d_offsets, d_rows, d_rowweight, d_rayweight, d_ticks, d_hits, d_counters, stream
+     end function srt_bin_rays_device
+     integer(c_int) function srt_bin_cells(params, ncells) bind(C, name="srt_bin_cells")
+       import :: c_int, c_int64_t, srt_bin_params
+       type(srt_bin_params), intent(in) :: params
+       integer(c_int64_t) :: ncells
+     end function srt_bin_cells
+     ! a map as text: ticks(ncells), hits(ncells) as type(c_ptr) (c_null_ptr = zeros)
+     integer(c_int) function srt_bin_file_write(path, params, ticks, hits) bind(C, name="srt_bin_file_write")
+       import :: c_int, c_char, c_ptr, srt_bin_params
+       character(kind=c_char), dimension(*) :: path
+       type(srt_bin_params), intent(in) :: params
+       type(c_ptr), value :: ticks, hits
+     end function srt_bin_file_write
+     ! edges, sum and hits come back as malloc'd C arrays (srt_free); params%axis(a)%edges point into edges
+     integer(c_int) function srt_bin_file_read(path, params, edges, ncells, sum, hits) bind(C, name="srt_bin_file_read")
+       import :: c_int, c_int64_t, c_char, c_ptr, srt_bin_params
+       character(kind=c_char), dimension(*) :: path
+       type(srt_bin_params) :: params
+       type(c_ptr) :: edges, sum, hits
+       integer(c_int64_t) :: ncells
+     end function srt_bin_file_read
      integer(c_int) function srt_model_nspec(model) bind(C, name="srt_model_nspec")
        import :: c_int, c_ptr
        type(c_ptr), value :: model

@@ -122,6 +122,40 @@ def crossings_device(packed, offsets, surfaces, capacity=None, stream=None):
     return ev, meta, count
 
 
+def bin_rays_device(packed, offsets, axes, nsub=8, quantum=2.0 ** -30, row_weight=None, ray_weight=None, out=None, stream=None):
+    """srt_bin_rays_device on torch CUDA tensors (packed[>= offsets[n], 20], offsets[n + 1] as pack_rows_device returns them;
+    row_weight[>= offsets[n]] and ray_weight[n] float64 or None) -> (ticks, hits, counters[4]), int64 tensors on the device, the
+    maps shaped [n2][n1][n0] with absent axes dropped.  The call ACCUMULATES: pass a previous call's result as `out` to add
+    further rays (shards, segments, launch sets) to the same map; out=None starts from zeros.  Nothing waits for the GPU but the
+    one 8-byte read of offsets[n]."""
+    import torch
+
+    from . import api
+
+    p = api.bin_params(axes, nsub, quantum)
+    shape = api.bin_shape(p)
+    api.bin_cells(p)  # (a bad grid is refused before anything is allocated)
+    n = offsets.shape[0] - 1
+    dev = offsets.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    if out is None:
+        ticks = torch.zeros(shape, dtype=torch.int64, device=dev)
+        hits = torch.zeros(shape, dtype=torch.int64, device=dev)
+        counters = torch.zeros(4, dtype=torch.int64, device=dev)
+    else:
+        ticks, hits, counters = out
+        if tuple(ticks.shape) != shape or tuple(hits.shape) != shape or not (ticks.is_contiguous() and hits.is_contiguous()):
+            raise ValueError("out holds maps of shape %s / %s, the grid's is %s" % (tuple(ticks.shape), tuple(hits.shape), shape))
+    if ray_weight is not None and ray_weight.shape[0] != n:
+        raise ValueError("ray_weight holds %d entries for %d rays" % (ray_weight.shape[0], n))
+    import ctypes as C
+    api._check(api.lib().srt_bin_rays_device(C.byref(p), n, offsets.data_ptr(), packed.data_ptr(),
+                                             row_weight.data_ptr() if row_weight is not None else None,
+                                             ray_weight.data_ptr() if ray_weight is not None else None,
+                                             ticks.data_ptr(), hits.data_ptr(), counters.data_ptr(), st.cuda_stream))
+    return ticks, hits, counters
+
+
 def _sync(t):
     if t.is_cuda:
         import torch
