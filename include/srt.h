@@ -544,6 +544,56 @@ int srt_bin_cells(const srt_bin_params *params, int64_t *ncells);
 int srt_bin_file_write(const char *path, const srt_bin_params *params, const int64_t *ticks, const int64_t *hits);
 int srt_bin_file_read(const char *path, srt_bin_params *params, double **edges, int64_t *ncells, double **sum, int64_t **hits);
 
+/* ---- closest approaches along the kept rows: which rays pass an observer point, when, how close, and in what state ----
+ * No piece of the reference does this (matlab/ only plots).  A point is not a surface, so the crossings above cannot answer it.
+ * Input is the PACKED layout of the crossings: offsets[nrays + 1] (offsets[0] = 0) and rows[offsets[nrays]][SRT_ROW].  Observers
+ * are nobs (1 .. SRT_MAXOBS) entries of srt_observer: x in SM metres, radius in metres (the detection radius).
+ * USABLE: the interval (j, j + 1) of one ray's consecutive kept rows is usable when the crossings' condition holds (t, pos and
+ * vgrel finite at both ends, t_{j+1} != t_j) and t_{j+1} > t_j.
+ * CURVE AND TEST FUNCTION: with the crossings' Hermite curve in its Delta form (h = t1 - t0, D = p1 - p0, m0 = C vg0 h,
+ * m1 = C vg1 h, c2 = 3 D - 2 m0 - m1, c3 = m0 + m1 - 2 D):
+ *   p(sigma) = p0 + sigma (m0 + sigma (c2 + sigma c3)),   p'(sigma) = m0 + sigma (2 c2 + 3 sigma c3),
+ *   f(sigma) = (p(sigma) - o) . p'(sigma)     (half the derivative of the squared distance to the observer o),
+ * every product and sum as written, unfused, summed x, y, z in that order.  At the ends f(0) = (p0 - o) . m0 and
+ * f(1) = (p1 - o) . m1, from the rows themselves.
+ * APPROACH: the interval holds an approach of observer m when f(0) < 0 and !(f(1) < 0): the ray is approaching at the start and
+ * no longer approaching at the end.  sigma* comes from 52 halvings of [0, 1]: a step keeps lo = mid where f(mid) < 0, else
+ * hi = mid; hi is returned.  A row exactly at the closest point therefore gives one event, at sigma = 1 of the interval before
+ * it, and none in the next.  d = sqrt(sum (p(sigma*) - o)^2); the approach is an EVENT exactly when d <= radius.
+ * An event is a row of SRT_ROW doubles in the kept-row layout exactly as a crossing's (t = t0 + sigma* h, pos = p(sigma*),
+ * columns 4 .. 19 linear in sigma*), four int32 -- the ray, the observer's index, the interval (0-based among the ray's kept
+ * rows), 0 -- and one double, d.  Events are ordered by (ray, interval, observer index).
+ * SAMPLING -- what is NOT an event: a ray whose first kept row already recedes from the observer; a ray whose last kept row still
+ * approaches it; an interval whose ends are both approaching or both not, whatever the curve does inside; an interval with a
+ * non-finite t, pos or vgrel at either end, or with t_{j+1} <= t_j.  Rows with vgrel = 0 are used as they stand (f = 0 is "not
+ * < 0").  The kept rows decide what can be seen, so outputper decides how often an approach is missed.
+ * The definition has no early reject; the implementation's (the hull of the cubic's Bezier points against the radius) is
+ * conservative and changes no event.
+ * SRT_EINVAL, by name, before the device is looked at: nobs outside 1 .. SRT_MAXOBS, null observers, a non-finite coordinate, a
+ * radius that is not finite or not > 0; host offsets that decrease or do not start at 0. */
+#define SRT_MAXOBS 65536
+typedef struct srt_observer {
+  double x[3];
+  double radius;
+} srt_observer;
+/* On buffers resident in device memory (`observers` is host memory).  d_event_rows[capacity][SRT_ROW], d_event_meta[capacity][4],
+ * d_event_dist[capacity], d_count one int64: it always receives the total; events beyond `capacity` are left out (the first
+ * `capacity` events of the defined order are kept).  capacity = 0 with NULL outputs is a count-only call.  The device is found
+ * from the buffers, as in srt_pack_rows_device.  The call reads d_offsets[nrays] (8 bytes) behind the work already on `stream`,
+ * to size its launches, and checks it against the allocation d_rows points into (at most 2^31 - 2 rows); it copies the
+ * observers up, runs its passes on `stream` and returns when they are done (its scratch is freed then). */
+int srt_approaches_device(int nobs, const srt_observer *observers, int64_t nrays, const int64_t *d_offsets, const double *d_rows,
+                          double *d_event_rows, int32_t *d_event_meta, double *d_event_dist, int64_t capacity, int64_t *d_count,
+                          void *stream);
+/* The same on host buffers; *event_rows[*nevents][SRT_ROW], *event_meta[*nevents][4] and *event_dist[*nevents] are malloc'd
+ * (srt_free; NULL when there are no events). */
+int srt_approaches(int nobs, const srt_observer *observers, int64_t nrays, const int64_t *offsets, const double *rows,
+                   int64_t *nevents, double **event_rows, int32_t **event_meta, double **event_dist);
+/* One record per event, (4 i10, 21 es24.15e3): raynum[e] (the caller's number of the event's ray), observer index + 1,
+ * interval + 1, 0, the distance, then the event's row, formatted as the .ray writer formats.  Pure host code, needs no GPU. */
+int srt_approaches_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
+                              const double *event_dist, const double *event_rows);
+
 /* ---- file formats of the boundary ---- */
 /* ray input file: 7 list-directed reals per line (raytracer_driver.f95:1146); returns count, fills
  * malloc'd arrays the caller frees with srt_free */

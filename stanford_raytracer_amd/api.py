@@ -66,6 +66,11 @@ class Surface(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double * 4)]
 
 
+class Observer(C.Structure):
+    """srt_observer of include/srt.h: a point x[3] in SM metres and its detection radius in metres; see observer_array()."""
+    _fields_ = [("x", C.c_double * 3), ("radius", C.c_double)]
+
+
 class BinAxis(C.Structure):
     """srt_bin_axis of include/srt.h: a coordinate kind, n cells, n + 1 edges in host memory; see axis() and axis_maglat()."""
     _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("edges", C.POINTER(C.c_double))]
@@ -77,6 +82,7 @@ class BinParams(C.Structure):
 
 
 MAXSURF = 16  # SRT_MAXSURF
+MAXOBS = 65536  # SRT_MAXOBS
 RUNNING = -1  # SRT_RUNNING: stopcond of a paused ray
 STATE = 17    # SRT_STATE: doubles in a paused ray's record
 
@@ -189,6 +195,10 @@ def lib():
     L.srt_crossings_device.argtypes = [C.c_int, C.POINTER(Surface), C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp]
     L.srt_crossings.argtypes = [C.c_int, C.POINTER(Surface), C.c_int64, i64p, dp, i64p, C.POINTER(dp), C.POINTER(ip)]
     L.srt_crossings_file_write.argtypes = [C.c_char_p, C.c_int64, i64p, ip, dp]
+    obp = C.POINTER(Observer)
+    L.srt_approaches_device.argtypes = [C.c_int, obp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, vp, vp]
+    L.srt_approaches.argtypes = [C.c_int, obp, C.c_int64, i64p, dp, i64p, C.POINTER(dp), C.POINTER(ip), C.POINTER(dp)]
+    L.srt_approaches_file_write.argtypes = [C.c_char_p, C.c_int64, i64p, ip, dp, dp]
     bpp = C.POINTER(BinParams)
     L.srt_bin_rays_device.argtypes = [bpp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.srt_bin_rays.argtypes = [bpp, C.c_int64, i64p, dp, dp, dp, C.POINTER(i64p), C.POINTER(i64p), i64p]
@@ -770,6 +780,66 @@ def write_crossings_file(path, raynum, meta, event_rows):
         raise ValueError("raynum, meta and event_rows name %d, %d and %d events" % (len(raynum), len(meta), len(event_rows)))
     _check(lib().srt_crossings_file_write(os.fsencode(path), len(meta), raynum.ctypes.data_as(C.POINTER(C.c_int64)),
                                           meta.ctypes.data_as(ip), _dp(event_rows)))
+
+
+# ---- closest approaches to observer points along the kept rows (include/srt.h) -------
+def observer_array(observers):
+    """Observers as the C ABI takes them -> (ctypes array, count): a sequence of Observer, or an array [n, 4] of x, y, z (SM
+    metres) and the detection radius (metres)."""
+    if isinstance(observers, np.ndarray) or (len(observers) and not isinstance(observers[0], Observer)):
+        a = _f64(observers).reshape(-1, 4)
+        arr = (Observer * max(len(a), 1))()
+        if len(a):
+            C.memmove(arr, a.ctypes.data, a.nbytes)
+        return arr, len(a)
+    observers = list(observers)
+    arr = (Observer * max(len(observers), 1))()
+    for i, o in enumerate(observers):
+        arr[i] = o
+    return arr, len(observers)
+
+
+def approaches(observers, offsets, rows):
+    """Each ray's closest approach to each observer, where it comes within the observer's radius, located on the cubic Hermite
+    curve through consecutive kept rows of a packed row set (offsets[n+1], rows[offsets[n], 20]) -> (event_rows[E, 20],
+    meta[E, 4] int32 = ray, observer index, interval, 0, dist[E]), ordered by (ray, interval, observer)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    rows = _f64(rows).reshape(-1, ROW)
+    if offsets.ndim != 1 or offsets.size < 1:
+        raise ValueError("offsets holds nrays + 1 entries")
+    if rows.shape[0] < offsets[-1]:
+        raise ValueError("offsets name %d rows, rows holds %d" % (offsets[-1], rows.shape[0]))
+    arr, no = observer_array(observers)
+    n, pe, pm, pd = C.c_int64(), dp(), ip(), dp()
+    _check(lib().srt_approaches(no, arr, offsets.size - 1, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(rows), C.byref(n),
+                                C.byref(pe), C.byref(pm), C.byref(pd)))
+    try:
+        ev = np.ctypeslib.as_array(pe, (n.value, ROW)).copy() if n.value else np.zeros((0, ROW))
+        meta = np.ctypeslib.as_array(pm, (n.value, 4)).copy() if n.value else np.zeros((0, 4), dtype=np.int32)
+        dist = np.ctypeslib.as_array(pd, (n.value,)).copy() if n.value else np.zeros(0)
+    finally:
+        lib().srt_free(pe)
+        lib().srt_free(pm)
+        lib().srt_free(pd)
+    return ev, meta, dist
+
+
+def approaches_padded(rows, nrows, outputper, observers):
+    """approaches() of rows[n, slots, 20], nrows[n] as Model.trace returns them: packs first."""
+    offsets, packed = pack_rows(rows, nrows, outputper)
+    return approaches(observers, offsets, packed)
+
+
+def write_approaches_file(path, raynum, meta, dist, event_rows):
+    """One record per event, (4 i10, 21 es24.15e3): raynum[e], observer index + 1, interval + 1, 0, the distance, the event's row."""
+    meta = np.ascontiguousarray(meta, dtype=np.int32).reshape(-1, 4)
+    event_rows = _f64(event_rows).reshape(-1, ROW)
+    dist = _f64(dist).reshape(-1)
+    raynum = np.ascontiguousarray(raynum, dtype=np.int64).reshape(-1)
+    if not (len(raynum) == len(meta) == len(event_rows) == len(dist)):
+        raise ValueError("raynum, meta, dist and event_rows name %d, %d, %d and %d events" % (len(raynum), len(meta), len(dist), len(event_rows)))
+    _check(lib().srt_approaches_file_write(os.fsencode(path), len(meta), raynum.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           meta.ctypes.data_as(ip), _dp(dist), _dp(event_rows)))
 
 
 # ---- traced rays binned onto a grid: dwell time and power maps (include/srt.h) -------

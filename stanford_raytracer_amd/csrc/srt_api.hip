@@ -32,6 +32,7 @@
 #include "srt_xform.hpp"
 #include "srt_crossings.hpp"
 #include "srt_binning.hpp"
+#include "srt_approaches.hpp"
 #include <hipcub/hipcub.hpp>
 
 using namespace srt;
@@ -2294,6 +2295,140 @@ extern "C" int srt_crossings(int nsurf, const srt_surface *surfaces, int64_t nra
   *nevents = n;
   *event_rows = er;
   *event_meta = em;
+  return SRT_OK;
+}
+
+// ---- closest approaches to observer points along packed rows (kernels and point functions: srt_approaches.hpp) ----
+extern "C" int srt_approaches_device(int nobs, const srt_observer *observers, int64_t nrays, const int64_t *d_offsets,
+                                     const double *d_rows, double *d_event_rows, int32_t *d_event_meta, double *d_event_dist,
+                                     int64_t capacity, int64_t *d_count, void *stream) {
+  namespace ap = srt::approaches;
+  char why[200];
+  if (ap::check_observers(nobs, observers, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_approaches_device: %s", why);
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_approaches_device: nrays = %lld is negative", (long long)nrays);
+  if (nrays >= (1ll << 31)) return srt_set_error(SRT_EINVAL, "srt_approaches_device: nrays = %lld: an event names its ray in an int32", (long long)nrays);
+  if (capacity < 0) return srt_set_error(SRT_EINVAL, "srt_approaches_device: capacity = %lld is negative", (long long)capacity);
+  if (!d_offsets || !d_count) return srt_set_error(SRT_EINVAL, "srt_approaches_device: null d_offsets or d_count");
+  if (capacity > 0 && (!d_event_rows || !d_event_meta || !d_event_dist))
+    return srt_set_error(SRT_EINVAL, "srt_approaches_device: capacity = %lld with a null output", (long long)capacity);
+  int dev = -1, rc;
+  {
+    const void *ptrs[6] = {d_offsets, d_count, d_rows, capacity > 0 ? (const void *)d_event_rows : nullptr,
+                           capacity > 0 ? (const void *)d_event_meta : nullptr, capacity > 0 ? (const void *)d_event_dist : nullptr};
+    if ((rc = device_of("srt_approaches_device", ptrs, 6, &dev))) return rc;
+  }
+  DeviceScope scope;
+  if ((rc = scope.enter(dev))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!within_allocation(d_offsets, ((size_t)nrays + 1) * sizeof(int64_t)))
+    return srt_set_error(SRT_EINVAL, "srt_approaches_device: d_offsets has no room for nrays + 1 = %lld entries", (long long)nrays + 1);
+  // the one thing the host has to know: how many rows there are
+  long long total = 0;
+  HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (total < 0) return srt_set_error(SRT_EINVAL, "srt_approaches_device: offsets[nrays] = %lld is negative", total);
+  if (total >= (1ll << 31) - 1) return srt_set_error(SRT_EINVAL, "srt_approaches_device: %lld rows are too many for one call (2^31 - 2 at most)", total);
+  if (total < 2) { // no interval
+    HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
+    return SRT_OK;
+  }
+  if (!d_rows) return srt_set_error(SRT_EINVAL, "srt_approaches_device: null d_rows");
+  if (!within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double)))
+    return srt_set_error(SRT_EINVAL, "srt_approaches_device: offsets[nrays] names %lld rows, more than the allocation of d_rows holds", total);
+  if (capacity > 0 && (!within_allocation(d_event_rows, (size_t)capacity * SRT_ROW * sizeof(double)) ||
+                       !within_allocation(d_event_meta, (size_t)capacity * 4 * sizeof(int32_t)) ||
+                       !within_allocation(d_event_dist, (size_t)capacity * sizeof(double))))
+    return srt_set_error(SRT_EINVAL, "srt_approaches_device: an output has no room for capacity = %lld events", (long long)capacity);
+  // Scratch: the observers, count[total] (4 B a row), evoff[total + 1] (8 B a row), the scan's own.  It is NOT taken from the
+  // stream-ordered allocator as the crossings take theirs: with hipMallocAsync / hipFreeAsync here, the second call of a process
+  // found recycled blocks and counted no events in 4 of 12 fresh processes on an MI355X (the first call never failed).  Plain
+  // allocations, a synchronous copy of the observers, and a wait for the stream before they are freed.
+  static_assert(sizeof(long long) == sizeof(int64_t), "int64");
+  DevBuf<srt_observer> d_obs;
+  DevBuf<uint32_t> count;
+  DevBuf<long long> evoff;
+  DevBytes tmp;
+  HIP_OK(evoff.alloc((size_t)total + 1));
+  HIP_OK(count.alloc((size_t)total));
+  HIP_OK(d_obs.alloc((size_t)nobs));
+  HIP_OK(hipMemcpy(d_obs.p, observers, (size_t)nobs * sizeof(srt_observer), hipMemcpyHostToDevice));
+  size_t need = 0;
+  auto counts = hipcub::TransformInputIterator<long long, ap::RowCount, hipcub::CountingInputIterator<long long>>(
+      hipcub::CountingInputIterator<long long>(0), ap::RowCount{count.p, total});
+  HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, evoff.p, (int)(total + 1), st));
+  HIP_OK(tmp.alloc(need ? need : 16));
+  long long blocks = (total + ap::BLOCK - 1) / ap::BLOCK;
+  if (blocks > 65536) blocks = 65536;
+  const double Cl = srt::crossings::light_speed();
+  hipLaunchKernelGGL(ap::approaches_kernel<false>, dim3((unsigned)blocks), dim3(ap::BLOCK), 0, st, Cl, nobs, (const srt_observer *)d_obs.p,
+                     (long long)nrays, (const long long *)d_offsets, total, d_rows, count.p, (const long long *)nullptr, 0ll,
+                     (double *)nullptr, (int32_t *)nullptr, (double *)nullptr);
+  hipError_t e = hipcub::DeviceScan::ExclusiveSum((void *)tmp.p, need, counts, evoff.p, (int)(total + 1), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_count, evoff.p + total, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && capacity > 0)
+    hipLaunchKernelGGL(ap::approaches_kernel<true>, dim3((unsigned)blocks), dim3(ap::BLOCK), 0, st, Cl, nobs, (const srt_observer *)d_obs.p,
+                       (long long)nrays, (const long long *)d_offsets, total, d_rows, count.p, (const long long *)evoff.p,
+                       (long long)capacity, d_event_rows, d_event_meta, d_event_dist);
+  if (e == hipSuccess) e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(st); // (also on the error path: the scratch goes away when this returns)
+  HIP_OK(e);
+  HIP_OK(es);
+  return SRT_OK;
+}
+
+extern "C" int srt_approaches(int nobs, const srt_observer *observers, int64_t nrays, const int64_t *offsets, const double *rows,
+                              int64_t *nevents, double **event_rows, int32_t **event_meta, double **event_dist) {
+  namespace ap = srt::approaches;
+  char why[200];
+  if (ap::check_observers(nobs, observers, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_approaches: %s", why);
+  if (!nevents || !event_rows || !event_meta || !event_dist) return srt_set_error(SRT_EINVAL, "srt_approaches: null output");
+  *nevents = 0;
+  *event_rows = nullptr;
+  *event_meta = nullptr;
+  *event_dist = nullptr;
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_approaches: nrays = %lld is negative", (long long)nrays);
+  if (!offsets) return srt_set_error(SRT_EINVAL, "srt_approaches: null offsets");
+  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_approaches: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
+  for (int64_t r = 0; r < nrays; ++r)
+    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_approaches: offsets decrease at ray %lld", (long long)r);
+  const int64_t total = offsets[nrays];
+  if (total > 0 && !rows) return srt_set_error(SRT_EINVAL, "srt_approaches: null rows");
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  if (total < 2) return SRT_OK;
+  DevBuf<double> d_rows, d_ev, d_dist;
+  DevBuf<int64_t> d_off, d_count;
+  DevBuf<int32_t> d_meta;
+  if ((rc = upload(d_rows, rows, (size_t)total * SRT_ROW))) return rc;
+  HIP_OK(d_off.alloc((size_t)nrays + 1));
+  HIP_OK(d_count.alloc(1));
+  HIP_OK(hipMemcpy(d_off.p, offsets, ((size_t)nrays + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if ((rc = srt_approaches_device(nobs, observers, nrays, d_off.p, d_rows.p, nullptr, nullptr, nullptr, 0, d_count.p, nullptr))) return rc;
+  int64_t n = 0;
+  HIP_OK(hipMemcpy(&n, d_count.p, sizeof n, hipMemcpyDeviceToHost));
+  if (n == 0) return SRT_OK;
+  HIP_OK(d_ev.alloc((size_t)n * SRT_ROW));
+  HIP_OK(d_meta.alloc((size_t)n * 4));
+  HIP_OK(d_dist.alloc((size_t)n));
+  if ((rc = srt_approaches_device(nobs, observers, nrays, d_off.p, d_rows.p, d_ev.p, d_meta.p, d_dist.p, n, d_count.p, nullptr))) return rc;
+  HIP_OK(hipDeviceSynchronize());
+  double *er = (double *)malloc((size_t)n * SRT_ROW * sizeof(double));
+  int32_t *em = (int32_t *)malloc((size_t)n * 4 * sizeof(int32_t));
+  double *ed = (double *)malloc((size_t)n * sizeof(double));
+  hipError_t e = er && em && ed ? hipMemcpy(er, d_ev.p, (size_t)n * SRT_ROW * sizeof(double), hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemcpy(em, d_meta.p, (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ed, d_dist.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    free(er);
+    free(em);
+    free(ed);
+    return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "srt_approaches: %lld events: %s", (long long)n, hipGetErrorString(e));
+  }
+  *nevents = n;
+  *event_rows = er;
+  *event_meta = em;
+  *event_dist = ed;
   return SRT_OK;
 }
 

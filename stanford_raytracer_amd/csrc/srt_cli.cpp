@@ -216,6 +216,11 @@ int main(int argc, char **argv) {
          "           the surfaces file holds one `kind p0 p1 p2 p3` per line (0 sphere: radius in m; 1 L-shell: L; 2 magnetic\n"
          "           latitude: radians; 3 plane: normal and offset; trailing values may be absent); one record per crossing:\n"
          "           raynum, surface, interval, direction (4 i10), then t, pos, vprel, vgrel, n, B0, Ns (20 es24.15e3)\n"
+         "           --approach_in=<.ray file> --approach_observers=<file> --approach_out=<file> [--device=N]: each ray's closest\n"
+         "           approach to observer points, located on the cubic Hermite curve through consecutive records; the observers\n"
+         "           file holds one `x y z radius` per line (SM metres; an approach is reported when it comes within the radius);\n"
+         "           one record per event: raynum, observer, interval, 0 (4 i10), then the distance and t, pos, vprel, vgrel, n,\n"
+         "           B0, Ns (21 es24.15e3)\n"
          "           --bin_in=<.ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=9.313225746154785e-10]\n"
          "           [--device=N]: the dwell-time map of the rays of an existing file: every interval of consecutive records is cut\n"
          "           into bin_nsub pieces on the cubic Hermite curve, each deposits its duration into the cell of its midpoint, in\n"
@@ -431,6 +436,98 @@ int main(int argc, char **argv) {
       fclose(f);
       printf(" %lld rays, %lld records\n", (long long)n, (long long)nrec);
       srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed);
+      return 0;
+    }
+  }
+  {
+    // ours: --approach_in=<existing .ray file> --approach_observers=<file> --approach_out=<file>: each ray's closest approach to
+    // the observer points of the second file (include/srt.h), without tracing
+    std::string ain, aobs, aout;
+    const bool have_in = getopt_named("approach_in", ain), have_obs = getopt_named("approach_observers", aobs),
+               have_out = getopt_named("approach_out", aout);
+    if (have_in || have_obs || have_out) {
+      need(have_in, "approach_in");
+      need(have_obs, "approach_observers");
+      need(have_out, "approach_out");
+      int device = 0;
+      get_int("device", device);
+      // one observer per line, list-directed as the surfaces file is: x y z radius
+      std::vector<srt_observer> obs;
+      {
+        FILE *sf = fopen(aobs.c_str(), "r");
+        if (!sf) {
+          fprintf(stderr, "raytracer: --approach_observers: cannot open %s\n", aobs.c_str());
+          return 1;
+        }
+        char line[1024];
+        int lineno = 0;
+        while (fgets(line, sizeof line, sf)) {
+          ++lineno;
+          double v[4] = {0, 0, 0, 0};
+          int nv = 0;
+          for (char *q = line; *q; ++q)
+            if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
+            else if (*q == 'd' || *q == 'D') *q = 'e';
+          char *q = line;
+          bool bad = false;
+          for (;;) {
+            while (*q == ' ') ++q;
+            if (!*q) break;
+            char *end = nullptr;
+            const double x = strtod(q, &end);
+            if (end == q || nv == 4) {
+              bad = true;
+              break;
+            }
+            v[nv++] = x;
+            q = end;
+          }
+          if (nv == 0 && !bad) continue; // an empty line
+          if (bad || nv != 4) {
+            fclose(sf);
+            fprintf(stderr, "raytracer: --approach_observers: %s, line %d: expected `x y z radius` (four numbers)\n", aobs.c_str(), lineno);
+            return 1;
+          }
+          obs.push_back(srt_observer{{v[0], v[1], v[2]}, v[3]});
+        }
+        fclose(sf);
+        if (obs.empty() || obs.size() > (size_t)SRT_MAXOBS) {
+          fprintf(stderr, "raytracer: --approach_observers: %s holds %zu observers (1 .. %d are taken)\n", aobs.c_str(), obs.size(), SRT_MAXOBS);
+          return 1;
+        }
+      }
+      int32_t nspec = 0;
+      double qs[4], ms[4], *w0 = nullptr, *packed = nullptr;
+      int64_t nrec = 0, *raynum = nullptr;
+      int32_t *stop = nullptr, *kept = nullptr;
+      const int64_t n = srt_read_ray_file(ain.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &packed);
+      if (n < 0) {
+        fprintf(stderr, "raytracer: --approach_in: %s\n", srt_last_error());
+        return 1;
+      }
+      std::vector<int64_t> offsets((size_t)n + 1, 0);
+      for (int64_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + kept[i];
+      int64_t nev = 0;
+      double *ev = nullptr, *dist = nullptr;
+      int32_t *meta = nullptr;
+      if (nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
+        CHECK(srt_init(device));
+        CHECK(srt_approaches((int)obs.size(), obs.data(), n, offsets.data(), packed, &nev, &ev, &meta, &dist));
+      } else {
+        // the observers are still looked at: a bad one is refused whatever the file holds
+        int64_t zero[1] = {0};
+        const int rc = srt_approaches((int)obs.size(), obs.data(), 0, zero, nullptr, &nev, &ev, &meta, &dist);
+        if (rc == SRT_EINVAL) {
+          fprintf(stderr, "raytracer: %s\n", srt_last_error());
+          return 1;
+        }
+        nev = 0;
+      }
+      std::vector<int64_t> evray((size_t)nev);
+      for (int64_t e = 0; e < nev; ++e) evray[e] = raynum[meta[4 * e]];
+      CHECK(srt_approaches_file_write(aout.c_str(), nev, evray.data(), meta, dist, ev));
+      printf(" %lld rays, %lld records, %zu observers, %lld approaches\n", (long long)n, (long long)nrec, obs.size(), (long long)nev);
+      srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed), srt_free(ev), srt_free(meta), srt_free(dist);
       return 0;
     }
   }

@@ -38,6 +38,11 @@ module srt_bindc
      real(c_double) :: quantum
      type(srt_bin_axis) :: axis(3)
   end type srt_bin_params
+  ! srt_observer of include/srt.h: a point in SM metres and its detection radius in metres
+  integer(c_int), parameter :: SRT_MAXOBS = 65536
+  type, bind(C) :: srt_observer
+     real(c_double) :: x(3), radius
+  end type srt_observer
   ! srt_segment: what one srt_trace_run_next hands out (valid until the next call on the run).  c_f_pointer turns the members
   ! into arrays: ray(nrays), offsets(nrays+1), rows(20, offsets(nrays+1)), nrows(nrays), stopcond(nrays)
   type, bind(C) :: srt_segment
@@ -218,6 +223,38 @@ module srt_bindc
        integer(c_int32_t), intent(in) :: event_meta(*)
        real(c_double), intent(in) :: event_rows(*)
      end function srt_crossings_file_write
+     ! closest approaches to observer points along packed kept rows: offsets(nrays+1), rows(20, offsets(nrays+1)); event_rows,
+     ! event_meta and event_dist come back as malloc'd C arrays (c_f_pointer to (20, nevents), (4, nevents), (nevents); srt_free)
+     integer(c_int) function srt_approaches(nobs, observers, nrays, offsets, rows, nevents, event_rows, event_meta, event_dist) &
+          bind(C, name="srt_approaches")
+       import :: c_int, c_int64_t, c_double, c_ptr, srt_observer
+       integer(c_int), value :: nobs
+       type(srt_observer), intent(in) :: observers(*)
+       integer(c_int64_t), value :: nrays
+       integer(c_int64_t), intent(in) :: offsets(*)
+       real(c_double), intent(in) :: rows(*)
+       integer(c_int64_t) :: nevents
+       type(c_ptr) :: event_rows, event_meta, event_dist
+     end function srt_approaches
+     ! the same on device buffers (all type(c_ptr), value, but the host array `observers`); asynchronous on `stream`
+     integer(c_int) function srt_approaches_device(nobs, observers, nrays, d_offsets, d_rows, d_event_rows, d_event_meta, &
+          d_event_dist, capacity, d_count, stream) bind(C, name="srt_approaches_device")
+       import :: c_int, c_int64_t, c_ptr, srt_observer
+       integer(c_int), value :: nobs
+       type(srt_observer), intent(in) :: observers(*)
+       integer(c_int64_t), value :: nrays, capacity
+       type(c_ptr), value :: d_offsets, d_rows, d_event_rows, d_event_meta, d_event_dist, d_count, stream
+     end function srt_approaches_device
+     ! one (4 i10, 21 es24.15e3) record per event: raynum(nevents), event_meta(4, nevents), event_dist(nevents), event_rows(20, nevents)
+     integer(c_int) function srt_approaches_file_write(path, nevents, raynum, event_meta, event_dist, event_rows) &
+          bind(C, name="srt_approaches_file_write")
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_char
+       character(kind=c_char), dimension(*) :: path
+       integer(c_int64_t), value :: nevents
+       integer(c_int64_t), intent(in) :: raynum(*)
+       integer(c_int32_t), intent(in) :: event_meta(*)
+       real(c_double), intent(in) :: event_dist(*), event_rows(*)
+     end function srt_approaches_file_write
      ! traced rays binned onto a grid: offsets(nrays+1), rows(20, offsets(nrays+1)), rowweight(offsets(nrays+1)) and
      ! rayweight(nrays) as type(c_ptr) (c_null_ptr = all ones; c_loc of a target array otherwise); ticks and hits come back as
      ! malloc'd C arrays of ncells int64 (c_f_pointer; srt_free); counters(4) = used, skipped, deposited, outside
