@@ -243,6 +243,18 @@ def interp_layout_choose(nspec, nx, ny, nz, free_bytes):
     return rc
 
 
+def _take(*arrays):
+    """Copies of the arrays the library handed over in one call, each given as (pointer, shape) or (pointer, shape, dtype) -> a
+    list of them.  Every pointer is srt_free'd here, also when a copy fails; a null pointer, which the library returns for
+    nothing, gives zeros (float64 unless a dtype is named)."""
+    try:
+        return [np.ctypeslib.as_array(a[0], a[1]).copy() if a[0] else np.zeros(a[1], dtype=a[2] if len(a) > 2 else np.float64)
+                for a in arrays]
+    finally:
+        for a in arrays:
+            lib().srt_free(a[0])
+
+
 def _check(rc):
     if rc != 0:
         raise SrtError("srt error %d: %s" % (rc, (lib().srt_last_error() or b"").decode()))
@@ -402,11 +414,7 @@ class Model:
         counts = (C.c_int64 * 6)()
         _check(lib().srt_build_samples(self.h, C.byref(sp), n_in, _dp(inp) if n_in else None, C.byref(n_out),
                                        C.byref(out), counts))
-        try:
-            res = np.ctypeslib.as_array(out, shape=(n_out.value, w)).copy() if n_out.value else np.empty((0, w))
-        finally:
-            lib().srt_free(out)
-        return res, list(counts)
+        return _take((out, (n_out.value, w)))[0], list(counts)
 
     def to_interp(self, nx, ny, nz, bounds, compder=False, yearday=2010001, msec=0, layout="expanded"):
         """A modelnum=3 model tabulating this one, built without leaving the device.  layout: as interp_file."""
@@ -732,26 +740,27 @@ def surface_array(surfaces):
     return arr, len(surfaces)
 
 
-def crossings(offsets, rows, surfaces):
-    """Where and when the rays of a packed row set (offsets[n+1], rows[offsets[n], 20]: read_ray_file, Model.trace_packed) cross
-    `surfaces`, located on the cubic Hermite curve through consecutive kept rows -> (event_rows[E, 20], meta[E, 4] int32 =
-    ray, surface index, interval, direction), ordered by (ray, interval, surface)."""
+def _packed(offsets, rows):
+    """A packed row set as the C ABI takes it -> (offsets int64[nrays + 1], rows float64[>= offsets[nrays], 20]), contiguous."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     rows = _f64(rows).reshape(-1, ROW)
     if offsets.ndim != 1 or offsets.size < 1:
         raise ValueError("offsets holds nrays + 1 entries")
     if rows.shape[0] < offsets[-1]:
         raise ValueError("offsets name %d rows, rows holds %d" % (offsets[-1], rows.shape[0]))
+    return offsets, rows
+
+
+def crossings(offsets, rows, surfaces):
+    """Where and when the rays of a packed row set (offsets[n+1], rows[offsets[n], 20]: read_ray_file, Model.trace_packed) cross
+    `surfaces`, located on the cubic Hermite curve through consecutive kept rows -> (event_rows[E, 20], meta[E, 4] int32 =
+    ray, surface index, interval, direction), ordered by (ray, interval, surface)."""
+    offsets, rows = _packed(offsets, rows)
     arr, ns = surface_array(surfaces)
     n, pe, pm = C.c_int64(), dp(), ip()
     _check(lib().srt_crossings(ns, arr, offsets.size - 1, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(rows), C.byref(n),
                                C.byref(pe), C.byref(pm)))
-    try:
-        ev = np.ctypeslib.as_array(pe, (n.value, ROW)).copy() if n.value else np.zeros((0, ROW))
-        meta = np.ctypeslib.as_array(pm, (n.value, 4)).copy() if n.value else np.zeros((0, 4), dtype=np.int32)
-    finally:
-        lib().srt_free(pe)
-        lib().srt_free(pm)
+    ev, meta = _take((pe, (n.value, ROW)), (pm, (n.value, 4), np.int32))
     return ev, meta
 
 
@@ -803,24 +812,12 @@ def approaches(observers, offsets, rows):
     """Each ray's closest approach to each observer, where it comes within the observer's radius, located on the cubic Hermite
     curve through consecutive kept rows of a packed row set (offsets[n+1], rows[offsets[n], 20]) -> (event_rows[E, 20],
     meta[E, 4] int32 = ray, observer index, interval, 0, dist[E]), ordered by (ray, interval, observer)."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    rows = _f64(rows).reshape(-1, ROW)
-    if offsets.ndim != 1 or offsets.size < 1:
-        raise ValueError("offsets holds nrays + 1 entries")
-    if rows.shape[0] < offsets[-1]:
-        raise ValueError("offsets name %d rows, rows holds %d" % (offsets[-1], rows.shape[0]))
+    offsets, rows = _packed(offsets, rows)
     arr, no = observer_array(observers)
     n, pe, pm, pd = C.c_int64(), dp(), ip(), dp()
     _check(lib().srt_approaches(no, arr, offsets.size - 1, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(rows), C.byref(n),
                                 C.byref(pe), C.byref(pm), C.byref(pd)))
-    try:
-        ev = np.ctypeslib.as_array(pe, (n.value, ROW)).copy() if n.value else np.zeros((0, ROW))
-        meta = np.ctypeslib.as_array(pm, (n.value, 4)).copy() if n.value else np.zeros((0, 4), dtype=np.int32)
-        dist = np.ctypeslib.as_array(pd, (n.value,)).copy() if n.value else np.zeros(0)
-    finally:
-        lib().srt_free(pe)
-        lib().srt_free(pm)
-        lib().srt_free(pd)
+    ev, meta, dist = _take((pe, (n.value, ROW)), (pm, (n.value, 4), np.int32), (pd, (n.value,)))
     return ev, meta, dist
 
 
@@ -893,12 +890,7 @@ def bin_rays(offsets, rows, axes, nsub=8, quantum=2.0 ** -30, row_weight=None, r
     weight x duration into the cell of its midpoint, in integer ticks of `quantum` seconds.  row_weight[offsets[n]] and
     ray_weight[n] are optional.  -> dict(sum = ticks * quantum as float64, ticks, hits (int64), all shaped [n2][n1][n0] with
     absent axes dropped, and counters[4] = intervals used, intervals skipped, samples deposited, samples outside)."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    rows = _f64(rows).reshape(-1, ROW)
-    if offsets.ndim != 1 or offsets.size < 1:
-        raise ValueError("offsets holds nrays + 1 entries")
-    if rows.shape[0] < offsets[-1]:
-        raise ValueError("offsets name %d rows, rows holds %d" % (offsets[-1], rows.shape[0]))
+    offsets, rows = _packed(offsets, rows)
     n = offsets.size - 1
     rw = yw = None
     if row_weight is not None:
@@ -915,13 +907,8 @@ def bin_rays(offsets, rows, axes, nsub=8, quantum=2.0 ** -30, row_weight=None, r
     counters = np.zeros(4, dtype=np.int64)
     _check(lib().srt_bin_rays(C.byref(p), n, offsets.ctypes.data_as(i64p), _dp(rows), _dp(rw) if rw is not None else None,
                               _dp(yw) if yw is not None else None, C.byref(pt), C.byref(ph), counters.ctypes.data_as(i64p)))
-    try:
-        nc, shape = bin_cells(p), bin_shape(p)
-        ticks = np.ctypeslib.as_array(pt, (nc,)).copy().reshape(shape)
-        hits = np.ctypeslib.as_array(ph, (nc,)).copy().reshape(shape)
-    finally:
-        lib().srt_free(pt)
-        lib().srt_free(ph)
+    nc, shape = bin_cells(p), bin_shape(p)
+    ticks, hits = (a.reshape(shape) for a in _take((pt, (nc,), np.int64), (ph, (nc,), np.int64)))
     return {"sum": ticks.astype(np.float64) * float(quantum), "ticks": ticks, "hits": hits, "counters": counters}
 
 
@@ -958,17 +945,13 @@ def read_bin_file(path):
     i64p = C.POINTER(C.c_int64)
     pe, ps, ph, nc = dp(), dp(), i64p(), C.c_int64()
     _check(lib().srt_bin_file_read(os.fsencode(path), C.byref(p), C.byref(pe), C.byref(nc), C.byref(ps), C.byref(ph)))
-    try:
+    shape = bin_shape(p)
+    try:  # (each axis' edges lie somewhere in the one array behind pe)
         axes = [(int(p.axis[a].kind), np.ctypeslib.as_array(p.axis[a].edges, (p.axis[a].n + 1,)).copy()) for a in range(p.naxes)]
-        shape = bin_shape(p)
-        out = {"axes": axes, "nsub": int(p.nsub), "quantum": float(p.quantum),
-               "sum": np.ctypeslib.as_array(ps, (nc.value,)).copy().reshape(shape),
-               "hits": np.ctypeslib.as_array(ph, (nc.value,)).copy().reshape(shape)}
     finally:
         lib().srt_free(pe)
-        lib().srt_free(ps)
-        lib().srt_free(ph)
-    return out
+        sums, hits = (a.reshape(shape) for a in _take((ps, (nc.value,)), (ph, (nc.value,), np.int64)))
+    return {"axes": axes, "nsub": int(p.nsub), "quantum": float(p.quantum), "sum": sums, "hits": hits}
 
 
 # ---- model-3 grid files: text of the reference's grid builder <-> binary side-format (host code, no GPU) -------
@@ -1037,10 +1020,7 @@ def read_dump_file(path):
     pf = dp()
     _check(lib().srt_dump_file_read(os.fsencode(path), dims, _dp(bounds), C.byref(pf)))
     nspec, nx, ny, nz = (int(v) for v in dims)
-    try:
-        f = np.ctypeslib.as_array(pf, shape=(nz * ny * nx * (4 * nspec + 3),)).copy().reshape(nz, ny, nx, 4 * nspec + 3)
-    finally:
-        lib().srt_free(pf)
+    f = _take((pf, (nz * ny * nx * (4 * nspec + 3),)))[0].reshape(nz, ny, nx, 4 * nspec + 3)
     return {"f": f, "bounds": bounds, "nspec": nspec}
 
 

@@ -2099,6 +2099,11 @@ struct KeptRows {
     return k < slots ? k : slots;
   }
 };
+// the blocks of a grid-stride launch over n items, `per` to a block: ceil(n / per), 65536 at most
+static unsigned grid_blocks(long long n, long long per) {
+  const long long blocks = (n + per - 1) / per;
+  return (unsigned)(blocks < 65536 ? blocks : 65536);
+}
 __global__ void pack_total_kernel(KeptRows kr, long long nrays, long long *offsets) {
   offsets[nrays] = offsets[nrays - 1] + kr(nrays - 1);
 }
@@ -2153,17 +2158,15 @@ extern "C" int srt_pack_rows_device(int32_t slots, int32_t outputper, int64_t nr
   HIP_OK(ef);
   // offsets[nrays] = offsets[nrays-1] + kept(nrays-1)
   hipLaunchKernelGGL(pack_total_kernel, dim3(1), dim3(1), 0, st, KeptRows{d_nrows, outputper, slots}, (long long)nrays, (long long *)d_offsets);
-  if (capacity_rows > 0) {
-    long long blocks = (nrays + 3) / 4;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (long long)nrays, (int)slots, d_rows,
+  if (capacity_rows > 0)
+    hipLaunchKernelGGL(pack_rows_kernel, dim3(grid_blocks(nrays, 4)), dim3(256), 0, st, (long long)nrays, (int)slots, d_rows,
                        (const long long *)d_offsets, d_packed, (long long)capacity_rows);
-  }
   HIP_OK(hipGetLastError());
   return SRT_OK;
 }
 
-// ---- surface crossings along packed rows (kernels and point functions: srt_crossings.hpp) ----
+// ---- what a packed row set must satisfy: offsets[nrays + 1], rows[offsets[nrays]][SRT_ROW] (layout and curve: srt_rows.hpp) ----
+// Said once for every entry point that takes one; `who` is the entry point's name, the prefix of every refusal.
 // does [q, q + bytes) lie inside the allocation q points into?  (true when the runtime cannot say)
 static bool within_allocation(const void *q, size_t bytes) {
   hipDeviceptr_t base = nullptr;
@@ -2175,6 +2178,48 @@ static bool within_allocation(const void *q, size_t bytes) {
   return (const char *)q + bytes <= (const char *)base + size;
 }
 
+// Host form: the row set in host memory.  -> offsets[nrays], or -1 with the refusal set (SRT_EINVAL)
+static int64_t packed_rows_host(const char *who, int64_t nrays, const int64_t *offsets, const double *rows) {
+  if (nrays < 0) return srt_set_error(-1, "%s: nrays = %lld is negative", who, (long long)nrays);
+  if (!offsets) return srt_set_error(-1, "%s: null offsets", who);
+  if (offsets[0] != 0) return srt_set_error(-1, "%s: offsets[0] = %lld: the first ray's rows start at 0", who, (long long)offsets[0]);
+  for (int64_t r = 0; r < nrays; ++r)
+    if (offsets[r + 1] < offsets[r]) return srt_set_error(-1, "%s: offsets decrease at ray %lld", who, (long long)r);
+  if (offsets[nrays] > 0 && !rows) return srt_set_error(-1, "%s: null rows", who);
+  return offsets[nrays];
+}
+
+// Device form, first half: the refusals made before any pointer is looked at, the one device that owns every buffer (`scope` is
+// entered there), and room in d_offsets for nrays + 1 entries.  `counter` names d_counter in the refusal (d_count, d_counters).
+// An entry point that writes events passes its capacity, and whether an output that capacity needs is null; others pass nullptr.
+static int packed_rows_device(const char *who, int64_t nrays, const int64_t *d_offsets, const void *d_counter, const char *counter,
+                              const int64_t *capacity, bool null_output, const void *const *ptrs, int nptrs, DeviceScope &scope) {
+  if (nrays < 0) return srt_set_error(SRT_EINVAL, "%s: nrays = %lld is negative", who, (long long)nrays);
+  if (capacity) {
+    if (nrays >= (1ll << 31)) return srt_set_error(SRT_EINVAL, "%s: nrays = %lld: an event names its ray in an int32", who, (long long)nrays);
+    if (*capacity < 0) return srt_set_error(SRT_EINVAL, "%s: capacity = %lld is negative", who, (long long)*capacity);
+  }
+  if (!d_offsets || !d_counter) return srt_set_error(SRT_EINVAL, "%s: null d_offsets or %s", who, counter);
+  if (null_output) return srt_set_error(SRT_EINVAL, "%s: capacity = %lld with a null output", who, (long long)*capacity);
+  int dev = -1, rc;
+  if ((rc = device_of(who, ptrs, nptrs, &dev))) return rc;
+  if ((rc = scope.enter(dev))) return rc;
+  if (!within_allocation(d_offsets, ((size_t)nrays + 1) * sizeof(int64_t)))
+    return srt_set_error(SRT_EINVAL, "%s: d_offsets has no room for nrays + 1 = %lld entries", who, (long long)nrays + 1);
+  return SRT_OK;
+}
+
+// Device form, second half: total = offsets[nrays] as the entry point fetched it (each decides when that 8-byte copy is enqueued
+// and waited for).  -> nullptr, or what is wrong with it: the refusal reads "<who>: offsets[nrays] = <total> <this>"
+static const char *packed_total_refusal(long long total, const double *d_rows) {
+  if (total < 0) return "is negative";
+  if (total >= (1ll << 31) - 1) return "rows are too many for one call (2^31 - 2 at most)";
+  if (total >= 2 && !d_rows) return "rows, and d_rows is null";
+  if (total >= 2 && !within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double))) return "rows, more than the allocation of d_rows holds";
+  return nullptr;
+}
+
+// ---- surface crossings along packed rows (kernels and point functions: srt_crossings.hpp) ----
 extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *d_offsets,
                                     const double *d_rows, double *d_event_rows, int32_t *d_event_meta, int64_t capacity,
                                     int64_t *d_count, void *stream) {
@@ -2182,35 +2227,24 @@ extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int6
   cx::Surfaces S;
   char why[200];
   if (cx::prepare(nsurf, surfaces, &S, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_crossings_device: %s", why);
-  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_crossings_device: nrays = %lld is negative", (long long)nrays);
-  if (nrays >= (1ll << 31)) return srt_set_error(SRT_EINVAL, "srt_crossings_device: nrays = %lld: an event names its ray in an int32", (long long)nrays);
-  if (capacity < 0) return srt_set_error(SRT_EINVAL, "srt_crossings_device: capacity = %lld is negative", (long long)capacity);
-  if (!d_offsets || !d_count) return srt_set_error(SRT_EINVAL, "srt_crossings_device: null d_offsets or d_count");
-  if (capacity > 0 && (!d_event_rows || !d_event_meta)) return srt_set_error(SRT_EINVAL, "srt_crossings_device: capacity = %lld with a null output", (long long)capacity);
-  int dev = -1, rc;
-  {
-    const void *ptrs[5] = {d_offsets, d_count, d_rows, capacity > 0 ? (const void *)d_event_rows : nullptr,
-                           capacity > 0 ? (const void *)d_event_meta : nullptr};
-    if ((rc = device_of("srt_crossings_device", ptrs, 5, &dev))) return rc;
-  }
+  const void *ptrs[5] = {d_offsets, d_count, d_rows, capacity > 0 ? (const void *)d_event_rows : nullptr,
+                         capacity > 0 ? (const void *)d_event_meta : nullptr};
   DeviceScope scope;
-  if ((rc = scope.enter(dev))) return rc;
+  // (an event call: its capacity is judged, and a null output that capacity needs is refused in its place in the order)
+  int rc = packed_rows_device("srt_crossings_device", nrays, d_offsets, d_count, "d_count", &capacity,
+                              capacity > 0 && (!d_event_rows || !d_event_meta), ptrs, 5, scope);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (!within_allocation(d_offsets, ((size_t)nrays + 1) * sizeof(int64_t)))
-    return srt_set_error(SRT_EINVAL, "srt_crossings_device: d_offsets has no room for nrays + 1 = %lld entries", (long long)nrays + 1);
   // the one thing the host has to know: how many rows there are
   long long total = 0;
   HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  if (total < 0) return srt_set_error(SRT_EINVAL, "srt_crossings_device: offsets[nrays] = %lld is negative", total);
-  if (total >= (1ll << 31) - 1) return srt_set_error(SRT_EINVAL, "srt_crossings_device: %lld rows are too many for one call (2^31 - 2 at most)", total);
+  if (const char *refuse = packed_total_refusal(total, d_rows))
+    return srt_set_error(SRT_EINVAL, "srt_crossings_device: offsets[nrays] = %lld %s", total, refuse);
   if (total < 2) { // no interval
     HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
     return SRT_OK;
   }
-  if (!d_rows) return srt_set_error(SRT_EINVAL, "srt_crossings_device: null d_rows");
-  if (!within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double)))
-    return srt_set_error(SRT_EINVAL, "srt_crossings_device: offsets[nrays] names %lld rows, more than the allocation of d_rows holds", total);
   if (capacity > 0 && (!within_allocation(d_event_rows, (size_t)capacity * SRT_ROW * sizeof(double)) ||
                        !within_allocation(d_event_meta, (size_t)capacity * 4 * sizeof(int32_t))))
     return srt_set_error(SRT_EINVAL, "srt_crossings_device: an output has no room for capacity = %lld events", (long long)capacity);
@@ -2227,14 +2261,13 @@ extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int6
   if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, evoff, (int)(total + 1), st);
   if (e == hipSuccess) e = hipMallocAsync(&tmp, need ? need : 16, st);
   if (e == hipSuccess) {
-    long long blocks = (total + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(cx::crossings_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, S, (long long)nrays,
+    const unsigned blocks = grid_blocks(total, 256);
+    hipLaunchKernelGGL(cx::crossings_count_kernel, dim3(blocks), dim3(256), 0, st, S, (long long)nrays,
                        (const long long *)d_offsets, total, d_rows, mask);
     e = hipcub::DeviceScan::ExclusiveSum(tmp, need, counts, evoff, (int)(total + 1), st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_count, evoff + total, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && capacity > 0)
-      hipLaunchKernelGGL(cx::crossings_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, st, S, (long long)nrays,
+      hipLaunchKernelGGL(cx::crossings_fill_kernel, dim3(blocks), dim3(256), 0, st, S, (long long)nrays,
                          (const long long *)d_offsets, total, d_rows, (const uint16_t *)mask, (const long long *)evoff,
                          (long long)capacity, d_event_rows, d_event_meta);
     if (e == hipSuccess) e = hipGetLastError();
@@ -2247,55 +2280,86 @@ extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int6
   return SRT_OK;
 }
 
-extern "C" int srt_crossings(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *offsets, const double *rows,
-                             int64_t *nevents, double **event_rows, int32_t **event_meta) {
-  namespace cx = srt::crossings;
-  cx::Surfaces S;
-  char why[200];
-  if (cx::prepare(nsurf, surfaces, &S, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_crossings: %s", why);
-  if (!nevents || !event_rows || !event_meta) return srt_set_error(SRT_EINVAL, "srt_crossings: null output");
+// device buffer -> a malloc'd host array of n elements, the caller's to srt_free; on an error *out stays null
+template <class T>
+static hipError_t download(T **out, const T *d, size_t n) {
+  T *h = (T *)malloc(n * sizeof(T));
+  const hipError_t e = h ? hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
+  if (e == hipSuccess) *out = h;
+  else free(h);
+  return e;
+}
+
+// a packed row set goes up: rows[total][SRT_ROW] and offsets[nrays + 1]
+static int upload_packed(int64_t nrays, const int64_t *offsets, const double *rows, int64_t total, DevBuf<int64_t> &d_off,
+                         DevBuf<double> &d_rows) {
+  const int rc = upload(d_rows, rows, (size_t)total * SRT_ROW);
+  if (rc) return rc;
+  HIP_OK(d_off.alloc((size_t)nrays + 1));
+  HIP_OK(hipMemcpy(d_off.p, offsets, ((size_t)nrays + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  return SRT_OK;
+}
+
+// The host form of an entry point that writes events: the row set is judged and goes up, a count-only call says how many events
+// there are, a second call fills room for exactly that many, and they come down into malloc'd arrays -- all of them, or none.
+// device_call(d_offsets, d_rows, d_event_rows, d_event_meta, d_event_dist, capacity, d_count) is the entry point's device form;
+// event_dist is null where the events carry no distance.  The caller has looked at its own arguments and outputs.
+template <class DeviceCall>
+static int host_events(const char *who, int64_t nrays, const int64_t *offsets, const double *rows, DeviceCall device_call,
+                       int64_t *nevents, double **event_rows, int32_t **event_meta, double **event_dist) {
   *nevents = 0;
   *event_rows = nullptr;
   *event_meta = nullptr;
-  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_crossings: nrays = %lld is negative", (long long)nrays);
-  if (!offsets) return srt_set_error(SRT_EINVAL, "srt_crossings: null offsets");
-  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_crossings: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
-  for (int64_t r = 0; r < nrays; ++r)
-    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_crossings: offsets decrease at ray %lld", (long long)r);
-  const int64_t total = offsets[nrays];
-  if (total > 0 && !rows) return srt_set_error(SRT_EINVAL, "srt_crossings: null rows");
+  if (event_dist) *event_dist = nullptr;
+  const int64_t total = packed_rows_host(who, nrays, offsets, rows);
+  if (total < 0) return SRT_EINVAL;
   DeviceScope srt_iscope_;
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
   if (total < 2) return SRT_OK;
-  DevBuf<double> d_rows, d_ev;
+  DevBuf<double> d_rows, d_ev, d_dist;
   DevBuf<int64_t> d_off, d_count;
   DevBuf<int32_t> d_meta;
-  if ((rc = upload(d_rows, rows, (size_t)total * SRT_ROW))) return rc;
-  HIP_OK(d_off.alloc((size_t)nrays + 1));
+  if ((rc = upload_packed(nrays, offsets, rows, total, d_off, d_rows))) return rc;
   HIP_OK(d_count.alloc(1));
-  HIP_OK(hipMemcpy(d_off.p, offsets, ((size_t)nrays + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if ((rc = srt_crossings_device(nsurf, surfaces, nrays, d_off.p, d_rows.p, nullptr, nullptr, 0, d_count.p, nullptr))) return rc;
+  if ((rc = device_call(d_off.p, d_rows.p, nullptr, nullptr, nullptr, 0, d_count.p))) return rc;
   int64_t n = 0;
   HIP_OK(hipMemcpy(&n, d_count.p, sizeof n, hipMemcpyDeviceToHost));
   if (n == 0) return SRT_OK;
   HIP_OK(d_ev.alloc((size_t)n * SRT_ROW));
   HIP_OK(d_meta.alloc((size_t)n * 4));
-  if ((rc = srt_crossings_device(nsurf, surfaces, nrays, d_off.p, d_rows.p, d_ev.p, d_meta.p, n, d_count.p, nullptr))) return rc;
+  if (event_dist) HIP_OK(d_dist.alloc((size_t)n));
+  if ((rc = device_call(d_off.p, d_rows.p, d_ev.p, d_meta.p, d_dist.p, n, d_count.p))) return rc;
   HIP_OK(hipDeviceSynchronize());
-  double *er = (double *)malloc((size_t)n * SRT_ROW * sizeof(double));
-  int32_t *em = (int32_t *)malloc((size_t)n * 4 * sizeof(int32_t));
-  hipError_t e = er && em ? hipMemcpy(er, d_ev.p, (size_t)n * SRT_ROW * sizeof(double), hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
-  if (e == hipSuccess) e = hipMemcpy(em, d_meta.p, (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost);
+  double *er = nullptr, *ed = nullptr;
+  int32_t *em = nullptr;
+  hipError_t e = download(&er, d_ev.p, (size_t)n * SRT_ROW);
+  if (e == hipSuccess) e = download(&em, d_meta.p, (size_t)n * 4);
+  if (e == hipSuccess && event_dist) e = download(&ed, d_dist.p, (size_t)n);
   if (e != hipSuccess) {
     free(er);
     free(em);
-    return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "srt_crossings: %lld events: %s", (long long)n, hipGetErrorString(e));
+    return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "%s: %lld events: %s", who, (long long)n, hipGetErrorString(e));
   }
   *nevents = n;
   *event_rows = er;
   *event_meta = em;
+  if (event_dist) *event_dist = ed;
   return SRT_OK;
+}
+
+extern "C" int srt_crossings(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *offsets, const double *rows,
+                             int64_t *nevents, double **event_rows, int32_t **event_meta) {
+  srt::crossings::Surfaces S;
+  char why[200];
+  if (srt::crossings::prepare(nsurf, surfaces, &S, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_crossings: %s", why);
+  if (!nevents || !event_rows || !event_meta) return srt_set_error(SRT_EINVAL, "srt_crossings: null output");
+  return host_events(
+      "srt_crossings", nrays, offsets, rows,
+      [&](const int64_t *d_off, const double *d_rows, double *d_ev, int32_t *d_meta, double *, int64_t capacity, int64_t *d_count) {
+        return srt_crossings_device(nsurf, surfaces, nrays, d_off, d_rows, d_ev, d_meta, capacity, d_count, nullptr);
+      },
+      nevents, event_rows, event_meta, nullptr);
 }
 
 // ---- closest approaches to observer points along packed rows (kernels and point functions: srt_approaches.hpp) ----
@@ -2305,36 +2369,24 @@ extern "C" int srt_approaches_device(int nobs, const srt_observer *observers, in
   namespace ap = srt::approaches;
   char why[200];
   if (ap::check_observers(nobs, observers, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_approaches_device: %s", why);
-  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_approaches_device: nrays = %lld is negative", (long long)nrays);
-  if (nrays >= (1ll << 31)) return srt_set_error(SRT_EINVAL, "srt_approaches_device: nrays = %lld: an event names its ray in an int32", (long long)nrays);
-  if (capacity < 0) return srt_set_error(SRT_EINVAL, "srt_approaches_device: capacity = %lld is negative", (long long)capacity);
-  if (!d_offsets || !d_count) return srt_set_error(SRT_EINVAL, "srt_approaches_device: null d_offsets or d_count");
-  if (capacity > 0 && (!d_event_rows || !d_event_meta || !d_event_dist))
-    return srt_set_error(SRT_EINVAL, "srt_approaches_device: capacity = %lld with a null output", (long long)capacity);
-  int dev = -1, rc;
-  {
-    const void *ptrs[6] = {d_offsets, d_count, d_rows, capacity > 0 ? (const void *)d_event_rows : nullptr,
-                           capacity > 0 ? (const void *)d_event_meta : nullptr, capacity > 0 ? (const void *)d_event_dist : nullptr};
-    if ((rc = device_of("srt_approaches_device", ptrs, 6, &dev))) return rc;
-  }
+  const void *ptrs[6] = {d_offsets, d_count, d_rows, capacity > 0 ? (const void *)d_event_rows : nullptr,
+                         capacity > 0 ? (const void *)d_event_meta : nullptr, capacity > 0 ? (const void *)d_event_dist : nullptr};
   DeviceScope scope;
-  if ((rc = scope.enter(dev))) return rc;
+  // (an event call, as srt_crossings_device: capacity, and the three outputs it needs)
+  int rc = packed_rows_device("srt_approaches_device", nrays, d_offsets, d_count, "d_count", &capacity,
+                              capacity > 0 && (!d_event_rows || !d_event_meta || !d_event_dist), ptrs, 6, scope);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (!within_allocation(d_offsets, ((size_t)nrays + 1) * sizeof(int64_t)))
-    return srt_set_error(SRT_EINVAL, "srt_approaches_device: d_offsets has no room for nrays + 1 = %lld entries", (long long)nrays + 1);
   // the one thing the host has to know: how many rows there are
   long long total = 0;
   HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  if (total < 0) return srt_set_error(SRT_EINVAL, "srt_approaches_device: offsets[nrays] = %lld is negative", total);
-  if (total >= (1ll << 31) - 1) return srt_set_error(SRT_EINVAL, "srt_approaches_device: %lld rows are too many for one call (2^31 - 2 at most)", total);
+  if (const char *refuse = packed_total_refusal(total, d_rows))
+    return srt_set_error(SRT_EINVAL, "srt_approaches_device: offsets[nrays] = %lld %s", total, refuse);
   if (total < 2) { // no interval
     HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
     return SRT_OK;
   }
-  if (!d_rows) return srt_set_error(SRT_EINVAL, "srt_approaches_device: null d_rows");
-  if (!within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double)))
-    return srt_set_error(SRT_EINVAL, "srt_approaches_device: offsets[nrays] names %lld rows, more than the allocation of d_rows holds", total);
   if (capacity > 0 && (!within_allocation(d_event_rows, (size_t)capacity * SRT_ROW * sizeof(double)) ||
                        !within_allocation(d_event_meta, (size_t)capacity * 4 * sizeof(int32_t)) ||
                        !within_allocation(d_event_dist, (size_t)capacity * sizeof(double))))
@@ -2357,16 +2409,15 @@ extern "C" int srt_approaches_device(int nobs, const srt_observer *observers, in
       hipcub::CountingInputIterator<long long>(0), ap::RowCount{count.p, total});
   HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, evoff.p, (int)(total + 1), st));
   HIP_OK(tmp.alloc(need ? need : 16));
-  long long blocks = (total + ap::BLOCK - 1) / ap::BLOCK;
-  if (blocks > 65536) blocks = 65536;
-  const double Cl = srt::crossings::light_speed();
-  hipLaunchKernelGGL(ap::approaches_kernel<false>, dim3((unsigned)blocks), dim3(ap::BLOCK), 0, st, Cl, nobs, (const srt_observer *)d_obs.p,
+  const unsigned blocks = grid_blocks(total, ap::BLOCK);
+  const double Cl = srt::rows::light_speed();
+  hipLaunchKernelGGL(ap::approaches_kernel<false>, dim3(blocks), dim3(ap::BLOCK), 0, st, Cl, nobs, (const srt_observer *)d_obs.p,
                      (long long)nrays, (const long long *)d_offsets, total, d_rows, count.p, (const long long *)nullptr, 0ll,
                      (double *)nullptr, (int32_t *)nullptr, (double *)nullptr);
   hipError_t e = hipcub::DeviceScan::ExclusiveSum((void *)tmp.p, need, counts, evoff.p, (int)(total + 1), st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_count, evoff.p + total, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
   if (e == hipSuccess && capacity > 0)
-    hipLaunchKernelGGL(ap::approaches_kernel<true>, dim3((unsigned)blocks), dim3(ap::BLOCK), 0, st, Cl, nobs, (const srt_observer *)d_obs.p,
+    hipLaunchKernelGGL(ap::approaches_kernel<true>, dim3(blocks), dim3(ap::BLOCK), 0, st, Cl, nobs, (const srt_observer *)d_obs.p,
                        (long long)nrays, (const long long *)d_offsets, total, d_rows, count.p, (const long long *)evoff.p,
                        (long long)capacity, d_event_rows, d_event_meta, d_event_dist);
   if (e == hipSuccess) e = hipGetLastError();
@@ -2382,54 +2433,12 @@ extern "C" int srt_approaches(int nobs, const srt_observer *observers, int64_t n
   char why[200];
   if (ap::check_observers(nobs, observers, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_approaches: %s", why);
   if (!nevents || !event_rows || !event_meta || !event_dist) return srt_set_error(SRT_EINVAL, "srt_approaches: null output");
-  *nevents = 0;
-  *event_rows = nullptr;
-  *event_meta = nullptr;
-  *event_dist = nullptr;
-  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_approaches: nrays = %lld is negative", (long long)nrays);
-  if (!offsets) return srt_set_error(SRT_EINVAL, "srt_approaches: null offsets");
-  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_approaches: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
-  for (int64_t r = 0; r < nrays; ++r)
-    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_approaches: offsets decrease at ray %lld", (long long)r);
-  const int64_t total = offsets[nrays];
-  if (total > 0 && !rows) return srt_set_error(SRT_EINVAL, "srt_approaches: null rows");
-  DeviceScope srt_iscope_;
-  int rc = srt_iscope_.enter_default();
-  if (rc) return rc;
-  if (total < 2) return SRT_OK;
-  DevBuf<double> d_rows, d_ev, d_dist;
-  DevBuf<int64_t> d_off, d_count;
-  DevBuf<int32_t> d_meta;
-  if ((rc = upload(d_rows, rows, (size_t)total * SRT_ROW))) return rc;
-  HIP_OK(d_off.alloc((size_t)nrays + 1));
-  HIP_OK(d_count.alloc(1));
-  HIP_OK(hipMemcpy(d_off.p, offsets, ((size_t)nrays + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  if ((rc = srt_approaches_device(nobs, observers, nrays, d_off.p, d_rows.p, nullptr, nullptr, nullptr, 0, d_count.p, nullptr))) return rc;
-  int64_t n = 0;
-  HIP_OK(hipMemcpy(&n, d_count.p, sizeof n, hipMemcpyDeviceToHost));
-  if (n == 0) return SRT_OK;
-  HIP_OK(d_ev.alloc((size_t)n * SRT_ROW));
-  HIP_OK(d_meta.alloc((size_t)n * 4));
-  HIP_OK(d_dist.alloc((size_t)n));
-  if ((rc = srt_approaches_device(nobs, observers, nrays, d_off.p, d_rows.p, d_ev.p, d_meta.p, d_dist.p, n, d_count.p, nullptr))) return rc;
-  HIP_OK(hipDeviceSynchronize());
-  double *er = (double *)malloc((size_t)n * SRT_ROW * sizeof(double));
-  int32_t *em = (int32_t *)malloc((size_t)n * 4 * sizeof(int32_t));
-  double *ed = (double *)malloc((size_t)n * sizeof(double));
-  hipError_t e = er && em && ed ? hipMemcpy(er, d_ev.p, (size_t)n * SRT_ROW * sizeof(double), hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
-  if (e == hipSuccess) e = hipMemcpy(em, d_meta.p, (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(ed, d_dist.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    free(er);
-    free(em);
-    free(ed);
-    return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "srt_approaches: %lld events: %s", (long long)n, hipGetErrorString(e));
-  }
-  *nevents = n;
-  *event_rows = er;
-  *event_meta = em;
-  *event_dist = ed;
-  return SRT_OK;
+  return host_events(
+      "srt_approaches", nrays, offsets, rows,
+      [&](const int64_t *d_off, const double *d_rows, double *d_ev, int32_t *d_meta, double *d_dist, int64_t capacity, int64_t *d_count) {
+        return srt_approaches_device(nobs, observers, nrays, d_off, d_rows, d_ev, d_meta, d_dist, capacity, d_count, nullptr);
+      },
+      nevents, event_rows, event_meta, event_dist);
 }
 
 // ---- traced rays binned onto a grid (kernel and point functions: srt_binning.hpp) ----
@@ -2453,18 +2462,12 @@ extern "C" int srt_bin_rays_device(const srt_bin_params *params, int64_t nrays, 
   char why[200];
   if (bn::prepare(params, &G, edges.data(), why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: %s", why);
   if (!d_ticks && !d_hits) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: both outputs (d_ticks and d_hits) are null");
-  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: nrays = %lld is negative", (long long)nrays);
-  if (!d_offsets || !d_counters) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: null d_offsets or d_counters");
-  int dev = -1, rc;
-  {
-    const void *ptrs[7] = {d_offsets, d_counters, d_rows, d_rowweight, d_rayweight, d_ticks, d_hits};
-    if ((rc = device_of("srt_bin_rays_device", ptrs, 7, &dev))) return rc;
-  }
+  const void *ptrs[7] = {d_offsets, d_counters, d_rows, d_rowweight, d_rayweight, d_ticks, d_hits};
   DeviceScope scope;
-  if ((rc = scope.enter(dev))) return rc;
+  // (no events: no capacity to judge, no output that depends on one)
+  int rc = packed_rows_device("srt_bin_rays_device", nrays, d_offsets, d_counters, "d_counters", nullptr, false, ptrs, 7, scope);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (!within_allocation(d_offsets, ((size_t)nrays + 1) * sizeof(int64_t)))
-    return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: d_offsets has no room for nrays + 1 = %lld entries", (long long)nrays + 1);
   if (!within_allocation(d_counters, 4 * sizeof(int64_t)) || (d_ticks && !within_allocation(d_ticks, (size_t)G.ncells * sizeof(int64_t))) ||
       (d_hits && !within_allocation(d_hits, (size_t)G.ncells * sizeof(int64_t))))
     return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: an output has no room for %lld cells (or d_counters for 4 counters)", G.ncells);
@@ -2480,11 +2483,8 @@ extern "C" int srt_bin_rays_device(const srt_bin_params *params, int64_t nrays, 
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   const char *refuse = nullptr;
   if (e == hipSuccess) {
-    if (total < 0) refuse = "is negative";
-    else if (total >= (1ll << 31) - 1) refuse = "rows are too many for one call (2^31 - 2 at most)";
-    else if (total >= 2 && !d_rows) refuse = "rows, and d_rows is null";
-    else if (total >= 2 && !within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double))) refuse = "rows, more than the allocation of d_rows holds";
-    else if (total >= 2 && d_rowweight && !within_allocation(d_rowweight, (size_t)total * sizeof(double))) refuse = "rows, more than the allocation of d_rowweight holds";
+    refuse = packed_total_refusal(total, d_rows);
+    if (!refuse && total >= 2 && d_rowweight && !within_allocation(d_rowweight, (size_t)total * sizeof(double))) refuse = "rows, more than the allocation of d_rowweight holds";
   }
   if (e == hipSuccess && !refuse && total >= 2) {
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(unsigned long long) == sizeof(int64_t), "int64");
@@ -2520,13 +2520,8 @@ extern "C" int srt_bin_rays(const srt_bin_params *params, int64_t nrays, const i
   if (hits) *hits = nullptr;
   if (!counters) return srt_set_error(SRT_EINVAL, "srt_bin_rays: null counters");
   for (int k = 0; k < 4; ++k) counters[k] = 0;
-  if (nrays < 0) return srt_set_error(SRT_EINVAL, "srt_bin_rays: nrays = %lld is negative", (long long)nrays);
-  if (!offsets) return srt_set_error(SRT_EINVAL, "srt_bin_rays: null offsets");
-  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_bin_rays: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
-  for (int64_t r = 0; r < nrays; ++r)
-    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_bin_rays: offsets decrease at ray %lld", (long long)r);
-  const int64_t total = offsets[nrays];
-  if (total > 0 && !rows) return srt_set_error(SRT_EINVAL, "srt_bin_rays: null rows");
+  const int64_t total = packed_rows_host("srt_bin_rays", nrays, offsets, rows);
+  if (total < 0) return SRT_EINVAL;
   DeviceScope srt_iscope_;
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
@@ -2536,20 +2531,18 @@ extern "C" int srt_bin_rays(const srt_bin_params *params, int64_t nrays, const i
   HIP_OK(d_out.alloc(4 + 2 * nc));
   HIP_OK(hipMemset(d_out.p, 0, (4 + 2 * nc) * sizeof(int64_t)));
   if (total >= 2) {
-    if ((rc = upload(d_rows, rows, (size_t)total * SRT_ROW))) return rc;
+    if ((rc = upload_packed(nrays, offsets, rows, total, d_off, d_rows))) return rc;
     if (rowweight && (rc = upload(d_roww, rowweight, (size_t)total))) return rc;
     if (rayweight && (rc = upload(d_rayw, rayweight, (size_t)nrays))) return rc;
-    HIP_OK(d_off.alloc((size_t)nrays + 1));
-    HIP_OK(hipMemcpy(d_off.p, offsets, ((size_t)nrays + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if ((rc = srt_bin_rays_device(params, nrays, d_off.p, d_rows.p, rowweight ? d_roww.p : nullptr, rayweight ? d_rayw.p : nullptr,
                                   ticks ? d_out.p + 4 : nullptr, hits ? d_out.p + 4 + nc : nullptr, d_out.p, nullptr)))
       return rc;
     HIP_OK(hipDeviceSynchronize());
   }
-  int64_t *ht = ticks ? (int64_t *)malloc(nc * sizeof(int64_t)) : nullptr, *hh = hits ? (int64_t *)malloc(nc * sizeof(int64_t)) : nullptr;
-  hipError_t e = (ticks && !ht) || (hits && !hh) ? hipErrorOutOfMemory : hipMemcpy(counters, d_out.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && ht) e = hipMemcpy(ht, d_out.p + 4, nc * sizeof(int64_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && hh) e = hipMemcpy(hh, d_out.p + 4 + nc, nc * sizeof(int64_t), hipMemcpyDeviceToHost);
+  int64_t *ht = nullptr, *hh = nullptr;
+  hipError_t e = hipMemcpy(counters, d_out.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && ticks) e = download(&ht, (const int64_t *)d_out.p + 4, nc);
+  if (e == hipSuccess && hits) e = download(&hh, (const int64_t *)d_out.p + 4 + nc, nc);
   if (e != hipSuccess) {
     free(ht);
     free(hh);

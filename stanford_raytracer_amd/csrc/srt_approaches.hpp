@@ -1,10 +1,10 @@
-// srt_approaches.hpp -- each ray's closest approach to observer points (include/srt.h, "closest approaches"): on the crossings'
-// cubic Hermite curve through two consecutive kept rows, the test function f = (p - o) . p', the bisection that locates its
+// srt_approaches.hpp -- each ray's closest approach to observer points (include/srt.h, "closest approaches"): on the cubic
+// Hermite curve through two consecutive kept rows (srt_rows.hpp), the test function f = (p - o) . p', the bisection that locates its
 // change from < 0 to >= 0, the distance there, and the two passes over packed rows x observers.
 //
 // Two halves, as srt_crossings.hpp has them.  The POINT FUNCTIONS are __host__ __device__ and spell out every operation with
 // contraction off, so that a host build (tests/native/approaches_host.cpp) and the device give the same bits: only +, -, * and
-// sqrt reach an event.  The interval, the curve, the event's row and the search in offsets are the crossings' own functions.
+// sqrt reach an event.  The interval, the curve, the event's row and the search in offsets are srt_rows.hpp's.
 // The KERNELS take one lane per packed row (the interval that starts there) and walk the observers, staged through LDS in tiles
 // that every lane reads at the same address (a broadcast).  A pair is first held against the hull of the cubic's Bezier points
 // -- about ten fp64 instructions -- and only a survivor pays for the end signs and the bisection.  A count pass writes one uint32
@@ -13,12 +13,10 @@
 //
 // Compiles for the device (hipcc) and for the host.
 #pragma once
-#include "srt_crossings.hpp"
+#include "srt_crossings.hpp" // (crossings::light_speed, which callers of this header pass as C; the curve: srt_rows.hpp)
 
 namespace srt {
 namespace approaches {
-
-namespace cx = srt::crossings;
 
 // Host: the refusals of include/srt.h, by name.  0 = fine; otherwise `why` says what is wrong.
 inline int check_observers(int nobs, const srt_observer *in, char *why, size_t whylen) {
@@ -44,18 +42,18 @@ inline int check_observers(int nobs, const srt_observer *in, char *why, size_t w
   return 0;
 }
 
-// usable for approaches: the crossings' condition, and time runs forward
-CX_HD inline bool interval_usable(const double *r0, const double *r1) { return cx::interval_usable(r0, r1) && r1[0] > r0[0]; }
+// usable for approaches: the condition of every packed-row consumer, and time runs forward
+ROWS_HD inline bool interval_usable(const double *r0, const double *r1) { return rows::interval_usable(r0, r1) && r1[0] > r0[0]; }
 
-// An interval as a pair that survives the hull test reads it: the crossings' curve and the far end as the rows give it
+// An interval as a pair that survives the hull test reads it: the curve and the far end as the rows give it
 // (p1, m1 = C vg1 h).
 struct Prepared {
-  cx::Interval iv;
+  rows::Interval iv;
   double p1[3], m1[3];
 };
-CX_HD inline void prepare(const double *r0, const double *r1, double C, Prepared &P) {
-  CX_NOCONTRACT
-  cx::interval_setup(r0, r1, C, P.iv);
+ROWS_HD inline void prepare(const double *r0, const double *r1, double C, Prepared &P) {
+  ROWS_NOCONTRACT
+  rows::interval_setup(r0, r1, C, P.iv);
   for (int c = 0; c < 3; ++c) {
     P.p1[c] = r1[1 + c];
     P.m1[c] = C * r1[7 + c] * P.iv.h;
@@ -69,8 +67,8 @@ CX_HD inline void prepare(const double *r0, const double *r1, double C, Prepared
 struct Ball {
   double c[3], reach;
 };
-CX_HD inline void ball_of(const double *r0, const double *r1, double C, Ball &B) {
-  CX_NOCONTRACT
+ROWS_HD inline void ball_of(const double *r0, const double *r1, double C, Ball &B) {
+  ROWS_NOCONTRACT
   const double h = r1[0] - r0[0];
   double q[4] = {0.0, 0.0, 0.0, 0.0}, mag = 0.0;
   for (int c = 0; c < 3; ++c) {
@@ -92,8 +90,8 @@ CX_HD inline void ball_of(const double *r0, const double *r1, double C, Ball &B)
 
 // the conservative reject: |o - c| > (radius + reach)(1 + 2^-20) cannot hold an event.  Anything not finite compares false or
 // rejects only what is truly far.
-CX_HD inline bool too_far(const Ball &B, const srt_observer &o) {
-  CX_NOCONTRACT
+ROWS_HD inline bool too_far(const Ball &B, const srt_observer &o) {
+  ROWS_NOCONTRACT
   const double dx = o.x[0] - B.c[0], dy = o.x[1] - B.c[1], dz = o.x[2] - B.c[2];
   const double d2 = dx * dx + dy * dy + dz * dz;
   const double thr = (o.radius + B.reach) * (1.0 + 0x1p-20);
@@ -101,14 +99,14 @@ CX_HD inline bool too_far(const Ball &B, const srt_observer &o) {
 }
 
 // f at an end, from the row itself: (p - o) . m
-CX_HD inline double end_f(const double p[3], const double m[3], const srt_observer &o) {
-  CX_NOCONTRACT
+ROWS_HD inline double end_f(const double p[3], const double m[3], const srt_observer &o) {
+  ROWS_NOCONTRACT
   return (p[0] - o.x[0]) * m[0] + (p[1] - o.x[1]) * m[1] + (p[2] - o.x[2]) * m[2];
 }
 
 // f(sigma) = (p(sigma) - o) . p'(sigma)
-CX_HD inline double approach_f(const cx::Interval &iv, const srt_observer &o, double sigma) {
-  CX_NOCONTRACT
+ROWS_HD inline double approach_f(const rows::Interval &iv, const srt_observer &o, double sigma) {
+  ROWS_NOCONTRACT
   double f = 0.0;
   for (int c = 0; c < 3; ++c) {
     const double x = iv.p0[c] + sigma * (iv.m0[c] + sigma * (iv.c2[c] + sigma * iv.c3[c]));
@@ -120,15 +118,15 @@ CX_HD inline double approach_f(const cx::Interval &iv, const srt_observer &o, do
 }
 
 // does the interval hold an approach of o: f(0) < 0 and !(f(1) < 0)
-CX_HD inline bool holds_approach(const Prepared &P, const srt_observer &o) {
+ROWS_HD inline bool holds_approach(const Prepared &P, const srt_observer &o) {
   return end_f(P.iv.p0, P.iv.m0, o) < 0.0 && !(end_f(P.p1, P.m1, o) < 0.0);
 }
 
 // sigma*: the crossings' locate with neg0 = true, on f
-CX_HD inline double locate(const cx::Interval &iv, const srt_observer &o) {
-  CX_NOCONTRACT
+ROWS_HD inline double locate(const rows::Interval &iv, const srt_observer &o) {
+  ROWS_NOCONTRACT
   double lo = 0.0, hi = 1.0;
-  for (int it = 0; it < cx::BISECTIONS; ++it) {
+  for (int it = 0; it < rows::BISECTIONS; ++it) {
     const double mid = 0.5 * (lo + hi);
     if (approach_f(iv, o, mid) < 0.0) lo = mid;
     else hi = mid;
@@ -137,30 +135,24 @@ CX_HD inline double locate(const cx::Interval &iv, const srt_observer &o) {
 }
 
 // the distance at sigma
-CX_HD inline double distance_at(const cx::Interval &iv, const srt_observer &o, double sigma) {
-  CX_NOCONTRACT
+ROWS_HD inline double distance_at(const rows::Interval &iv, const srt_observer &o, double sigma) {
+  ROWS_NOCONTRACT
   double x[3];
-  cx::hermite(iv, sigma, x);
+  rows::hermite(iv, sigma, x);
   const double dx = x[0] - o.x[0], dy = x[1] - o.x[1], dz = x[2] - o.x[2];
   return sqrt(dx * dx + dy * dy + dz * dz);
 }
 
 // The per-(interval, observer) decision behind the reject and the end signs: locate, measure, compare.
-CX_HD inline bool approach_event(const Prepared &P, const srt_observer &o, double *sigma, double *dist) {
+ROWS_HD inline bool approach_event(const Prepared &P, const srt_observer &o, double *sigma, double *dist) {
   *sigma = locate(P.iv, o);
   *dist = distance_at(P.iv, o, *sigma);
   return *dist <= o.radius;
 }
 
-// is (j, j + 1) an interval of one ray?  -> its ray, or -1
-CX_HD inline long long interval_ray(const long long *offsets, long long nrays, long long j) {
-  const long long r = cx::ray_of_row(offsets, nrays, j);
-  return (r < 0 || j + 1 >= offsets[r + 1]) ? -1 : r;
-}
-
-CX_HD inline void write_event(const Prepared &P, const double *r0, const double *r1, double sigma, double dist, long long ray,
-                              int obs, long long interval, long long e, double *ev_rows, int32_t *ev_meta, double *ev_dist) {
-  cx::event_row(P.iv, r0, r1, sigma, ev_rows + e * SRT_ROW);
+ROWS_HD inline void write_event(const Prepared &P, const double *r0, const double *r1, double sigma, double dist, long long ray,
+                                int obs, long long interval, long long e, double *ev_rows, int32_t *ev_meta, double *ev_dist) {
+  rows::event_row(P.iv, r0, r1, sigma, ev_rows + e * SRT_ROW);
   int32_t *q = ev_meta + e * 4;
   q[0] = (int32_t)ray;
   q[1] = obs;
@@ -178,14 +170,14 @@ struct RowState {
   bool live;
 };
 // one pair that the hull test let through; false: the walk of this row is over
-CX_HD inline bool row_pair(double C, const double *r0, const double *r1, long long nrays, const long long *offsets,
-                           long long j, const srt_observer &o, int index, RowState &st, uint32_t want, long long capacity,
-                           double *ev_rows, int32_t *ev_meta, double *ev_dist) {
+ROWS_HD inline bool row_pair(double C, const double *r0, const double *r1, long long nrays, const long long *offsets,
+                             long long j, const srt_observer &o, int index, RowState &st, uint32_t want, long long capacity,
+                             double *ev_rows, int32_t *ev_meta, double *ev_dist) {
   Prepared P; // (made again for each of the few survivors, from rows the caches hold: the walk itself keeps only the ball)
   prepare(r0, r1, C, P);
   if (!holds_approach(P, o)) return true;
   if (st.ray == -2) { // only a row with a survivor pays for the search in offsets
-    st.ray = interval_ray(offsets, nrays, j);
+    st.ray = rows::interval_ray(offsets, nrays, j);
     if (st.ray < 0) {
       st.live = false;
       return false;
@@ -208,9 +200,9 @@ CX_HD inline bool row_pair(double C, const double *r0, const double *r1, long lo
 // The hull test runs over WALK observers at a time without a branch, so that their reads are in flight together; the few pairs
 // it lets through are then taken in ascending order.
 constexpr int WALK = 8;
-CX_HD inline void row_walk(const Ball &B, double C, const double *r0, const double *r1, long long nrays, const long long *offsets,
-                           long long j, const srt_observer *obs, int n, int first, RowState &st, uint32_t want, long long capacity,
-                           double *ev_rows, int32_t *ev_meta, double *ev_dist) {
+ROWS_HD inline void row_walk(const Ball &B, double C, const double *r0, const double *r1, long long nrays, const long long *offsets,
+                             long long j, const srt_observer *obs, int n, int first, RowState &st, uint32_t want, long long capacity,
+                             double *ev_rows, int32_t *ev_meta, double *ev_dist) {
   int m = 0;
   for (; m + WALK <= n; m += WALK) {
     unsigned near = 0u;

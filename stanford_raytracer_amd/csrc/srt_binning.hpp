@@ -1,5 +1,5 @@
 // srt_binning.hpp -- traced rays binned onto a grid (include/srt.h, "dwell time and power maps"): the coordinate functions of
-// an axis, the half-open edge search, the midpoint samples of an interval on srt_crossings.hpp's own Hermite curve, their
+// an axis, the half-open edge search, the midpoint samples of an interval on srt_rows.hpp's Hermite curve, their
 // weights and deposits in integer ticks, the whole routine of one packed row, and the kernel over packed rows.
 //
 // Two halves, as srt_crossings.hpp.  The POINT FUNCTIONS are __host__ __device__ and spell out every operation with contraction
@@ -15,16 +15,10 @@
 //
 // Compiles for the device (hipcc) and for the host.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include "srt_crossings.hpp"
+#include "srt_rows.hpp"
 
 namespace srt {
 namespace binning {
-
-namespace cx = srt::crossings;
 
 constexpr int MAXN = 1024;                // cells per axis
 constexpr int MAXSUB = 64;                // samples per interval
@@ -65,7 +59,7 @@ inline int prepare(const srt_bin_params *p, Grid *G, double *edges, char *why, s
   G->naxes = p->naxes;
   G->nsub = p->nsub;
   G->quantum = p->quantum;
-  G->C = cx::light_speed();
+  G->C = rows::light_speed();
   G->ncells = 1;
   G->nedges = 0;
   for (int a = 0; a < 3; ++a) G->kind[a] = 0, G->n[a] = 1, G->eoff[a] = 0;
@@ -120,8 +114,8 @@ inline int prepare(const srt_bin_params *p, Grid *G, double *edges, char *why, s
 }
 
 // the coordinate of kind k at x (SM metres); not finite where it is not defined (L on the z axis, sinlat at the origin)
-CX_HD inline double coordinate(int kind, const double x[3]) {
-  CX_NOCONTRACT
+ROWS_HD inline double coordinate(int kind, const double x[3]) {
+  ROWS_NOCONTRACT
   if (kind < 3) return x[kind];
   if (kind == 7) return fmod(24.0 * atan2(x[1], x[0]) / (2.0 * PI) + 12.0, 24.0);
   const double rho2 = x[0] * x[0] + x[1] * x[1];
@@ -129,12 +123,12 @@ CX_HD inline double coordinate(int kind, const double x[3]) {
   const double r2 = rho2 + x[2] * x[2];
   const double r = sqrt(r2);
   if (kind == 3) return r;
-  if (kind == 5) return r2 * r / (cx::EARTH_RADIUS * rho2);
+  if (kind == 5) return r2 * r / (rows::EARTH_RADIUS * rho2);
   return x[2] / r;
 }
 
 // the cell of c on an axis of n cells: i with e[i] <= c < e[i + 1]; -1 when c is outside [e[0], e[n]) or not a number
-CX_HD inline int find_cell(const double *e, int n, double c) {
+ROWS_HD inline int find_cell(const double *e, int n, double c) {
   if (!(c >= e[0]) || !(c < e[n])) return -1;
   int lo = 0, hi = n;
   while (hi - lo > 1) {
@@ -146,7 +140,7 @@ CX_HD inline int find_cell(const double *e, int n, double c) {
 }
 
 // the cell index of x, (i2 n1 + i1) n0 + i0; -1 = outside
-CX_HD inline long long cell_of(const Grid &G, const double *edges, const double x[3]) {
+ROWS_HD inline long long cell_of(const Grid &G, const double *edges, const double x[3]) {
   long long cell = 0, mul = 1;
   for (int a = 0; a < G.naxes; ++a) {
     const int i = find_cell(edges + G.eoff[a], G.n[a], coordinate(G.kind[a], x));
@@ -158,18 +152,18 @@ CX_HD inline long long cell_of(const Grid &G, const double *edges, const double 
 }
 
 // sample k of nsub: sigma = (k + 1/2) / nsub
-CX_HD inline double sample_sigma(int k, int nsub) {
-  CX_NOCONTRACT
+ROWS_HD inline double sample_sigma(int k, int nsub) {
+  ROWS_NOCONTRACT
   return ((double)k + 0.5) / (double)nsub;
 }
 // W = rayweight (w0 + sigma (w1 - w0))
-CX_HD inline double sample_weight(double rayw, double w0, double w1, double sigma) {
-  CX_NOCONTRACT
+ROWS_HD inline double sample_weight(double rayw, double w0, double w1, double sigma) {
+  ROWS_NOCONTRACT
   return rayw * (w0 + sigma * (w1 - w0));
 }
 // d / quantum of a sample, d = W hsub, hsub = h / nsub
-CX_HD inline double sample_ticks(double W, double hsub, double quantum) {
-  CX_NOCONTRACT
+ROWS_HD inline double sample_ticks(double W, double hsub, double quantum) {
+  ROWS_NOCONTRACT
   return W * hsub / quantum;
 }
 
@@ -178,24 +172,24 @@ CX_HD inline double sample_ticks(double W, double hsub, double quantum) {
 // intervals used, intervals skipped, samples deposited, samples outside.  The pair of rows either side of a ray boundary is no
 // interval: it is neither used nor skipped.
 template <class Acc>
-CX_HD inline void bin_row(const Grid &G, const double *edges, long long nrays, const long long *offsets, long long total,
-                          const double *rows, const double *rowweight, const double *rayweight, long long j, Acc &acc,
-                          unsigned long long c[4]) {
+ROWS_HD inline void bin_row(const Grid &G, const double *edges, long long nrays, const long long *offsets, long long total,
+                            const double *rows, const double *rowweight, const double *rayweight, long long j, Acc &acc,
+                            unsigned long long c[4]) {
   if (j + 1 >= total) return;
-  const long long r = cx::ray_of_row(offsets, nrays, j);
+  const long long r = rows::ray_of_row(offsets, nrays, j);
   if (r < 0 || j + 1 >= offsets[r + 1]) return;
   const double *r0 = rows + j * SRT_ROW, *r1 = r0 + SRT_ROW;
   const bool weighted = rowweight || rayweight;
   const double w0 = rowweight ? rowweight[j] : 1.0, w1 = rowweight ? rowweight[j + 1] : 1.0, rayw = rayweight ? rayweight[r] : 1.0;
-  if (!cx::interval_usable(r0, r1) || !__builtin_isfinite(w0) || !__builtin_isfinite(w1) || !__builtin_isfinite(rayw)) {
+  if (!rows::interval_usable(r0, r1) || !__builtin_isfinite(w0) || !__builtin_isfinite(w1) || !__builtin_isfinite(rayw)) {
     c[1] += 1;
     return;
   }
-  cx::Interval iv;
-  cx::interval_setup(r0, r1, G.C, iv);
+  rows::Interval iv;
+  rows::interval_setup(r0, r1, G.C, iv);
   double hsub;
   {
-    CX_NOCONTRACT
+    ROWS_NOCONTRACT
     hsub = iv.h / (double)G.nsub;
   }
   // a deposit of 2^62 ticks or more (or none that is a number) at ANY sample skips the interval whole: looked at first
@@ -213,7 +207,7 @@ CX_HD inline void bin_row(const Grid &G, const double *edges, long long nrays, c
   for (int k = 0; k < G.nsub; ++k) {
     const double sigma = sample_sigma(k, G.nsub);
     double x[3];
-    cx::hermite(iv, sigma, x);
+    rows::hermite(iv, sigma, x);
     const long long cell = cell_of(G, edges, x);
     if (cell < 0) {
       c[3] += 1;

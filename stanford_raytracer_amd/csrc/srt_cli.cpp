@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <future>
 #include <memory>
 #include <string>
@@ -173,574 +174,486 @@ static int make_model(int device, srt_model **out, double *del) {
   return 0;
 }
 
-int main(int argc, char **argv) {
-  g_argc = argc;
-  g_argv = argv;
-  if (argc == 1) {
-    puts("Usage:\n  raytracer --param1=value1 --param2=value2 ...\n"
-         "  --dt0 --dtmax --tmax --root --fixedstep --maxerr --maxsteps --minalt\n"
-         "  --inputraysfile --outputfile --outputper\n"
-         "  --modelnum  (1) Ngo model  (3) interpolated model (gridded)  (4) interpolated model (scattered)\n"
-         "              (6) simplified GCPM (closed form)  (7) AT64ThCh (one field-line trace per evaluated point)\n"
-         "  model 1: --ngo_configfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1 --tsyganenko_Pdyn .. _W6\n"
-         "  model 3: --interp_interpfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1\n"
-         "           [--interp_layout=expanded|nodes|auto: the table on the device; nodes = an eighth of the bytes, slower]\n"
-         "  model 4: model 3 flags + --scattered_interp_window_scale --scattered_interp_order\n"
-         "           --scattered_interp_exact --scattered_interp_local_window_scale\n"
-         "           [--scattered_interp_root_sample=N: record N of the file is the root of the reference's kd-tree (spacing 0)]\n"
-         "  model 6: --kp --yearday --milliseconds_day [--fixed_MLT=1 --MLT=<hours>] --use_tsyganenko=0|1 --use_igrf=0|1\n"
-         "           --tsyganenko_Pdyn .. _W6  (--ngo_configfile is accepted and ignored, as by the reference's driver)\n"
-         "  model 7: --gcpm_kp=<integer> --yearday --milliseconds_day --tsyganenko_Pdyn .. _W6 (all ten, also with\n"
-         "           --use_tsyganenko=0: the model's field-line trace always runs through T04_s + IGRF)\n"
-         "           --use_tsyganenko=0|1 --use_igrf=0|1 [--igrf_coeffs=<table>]\n"
-         "  extra:   --device=N | --devices=0,1,..  --chunk_rays=N  --ray_order=0|1  --timing=1 (wall clock per phase)\n"
-         "           --segment_rows=N: trace in segments of N kept rows per ray and launch (rays are paused and resumed; device\n"
-         "             memory for chunk_rays * N rows instead of chunk_rays * maxsteps / outputper, the same .ray file; chunks of\n"
-         "             262144 rays unless --chunk_rays says otherwise; not together with --damping_out).  0 / absent: one launch per chunk\n"
-         "           --first_attempt_policy=1|0: error estimate of a ray's first adaptive attempt, where the reference reads an\n"
-         "             unset variable: 1 (default) = from the k term alone, as the reference's gfortran build behaves;\n"
-         "             0 = NaN => accepted at dt0, dt not grown, as a flang build behaves (the goldens of this repository)\n"
-         "  tools:   --grid2bin_in=<text grid> --grid2bin_out=<binary grid>   (convert and exit; --interp_interpfile\n"
-         "           accepts either form);  --pts2bin_in / --pts2bin_out: the same for model-4 sample files\n"
-         "           --buildgrid=1 --filename=<out> --minx .. --maxz --nx --ny --nz --compder=0|1 (the reference's regular grid\n"
-         "           builder gcpm_dens_model_buildgrid with the model of --modelnum in place of GCPM; --binary=1)\n"
-         "           --buildsamples=1 --filename=<out> --minx .. --maxz --n_initial_uniform ... (the reference's random grid\n"
-         "           builder with the model of --modelnum in place of GCPM; --seed, --binary=1)\n"
-         "           --dumpmodel=1 --filename=<out> --minx .. --maxz --nx --ny --nz (the reference's dumpmodel: qs, Ns, ms, nus, B0\n"
-         "           of the model of --modelnum at every node; an axis may have one node; --mag_coords=1 with model 6 or 7: the\n"
-         "           grid is in MAG coordinates)\n"
-         "           --damping_out=<file>: hot-plasma damping along the kept rows (raynum, row, t, rate, magnitude, flag);\n"
-         "           with --damping_in=<.ray file> instead of tracing: along the records of an existing file\n"
-         "           --crossings_in=<.ray file> --crossings_surfaces=<file> --crossings_out=<file> [--device=N]: where and when the\n"
-         "           rays of an existing file cross surfaces, located on the cubic Hermite curve through consecutive records;\n"
-         "           the surfaces file holds one `kind p0 p1 p2 p3` per line (0 sphere: radius in m; 1 L-shell: L; 2 magnetic\n"
-         "           latitude: radians; 3 plane: normal and offset; trailing values may be absent); one record per crossing:\n"
-         "           raynum, surface, interval, direction (4 i10), then t, pos, vprel, vgrel, n, B0, Ns (20 es24.15e3)\n"
-         "           --approach_in=<.ray file> --approach_observers=<file> --approach_out=<file> [--device=N]: each ray's closest\n"
-         "           approach to observer points, located on the cubic Hermite curve through consecutive records; the observers\n"
-         "           file holds one `x y z radius` per line (SM metres; an approach is reported when it comes within the radius);\n"
-         "           one record per event: raynum, observer, interval, 0 (4 i10), then the distance and t, pos, vprel, vgrel, n,\n"
-         "           B0, Ns (21 es24.15e3)\n"
-         "           --bin_in=<.ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=9.313225746154785e-10]\n"
-         "           [--device=N]: the dwell-time map of the rays of an existing file: every interval of consecutive records is cut\n"
-         "           into bin_nsub pieces on the cubic Hermite curve, each deposits its duration into the cell of its midpoint, in\n"
-         "           whole ticks of bin_quantum seconds; the axes file holds one axis per line, `kind n e0 e1 .. en` (kind 0 .. 7\n"
-         "           or x y z r rho L sinlat mlt; metres, L, sine of the magnetic latitude, hours; 1 .. 3 axes of 1 .. 1024 cells);\n"
-         "           the output holds the grid, then per cell seconds (es24.15e3) and samples (i20)");
+// ---- readers the modes share ----
+// --minx .. --maxz, all six required (gcpm_dens_model_buildgrid.f95:42-160, gcpm_dens_model_buildgrid_random.f95:56-90, dumpmodel.f95:167-213)
+static void need_bounds(double b[6]) {
+  const char *bn[6] = {"minx", "maxx", "miny", "maxy", "minz", "maxz"};
+  for (int k = 0; k < 6; ++k) need(get_real(bn[k], b[k]), bn[k]);
+}
+// the bounds and --nx --ny --nz (read as reals and floored) of a regular grid.  An axis with fewer than `least` nodes, or more
+// than an int holds, is refused with `refusal`, a format that takes the flag's name.  -> 0, or the exit code
+static int need_grid(double b[6], int n3[3], double least, const char *refusal) {
+  need_bounds(b);
+  const char *nn[3] = {"nx", "ny", "nz"};
+  for (int k = 0; k < 3; ++k) {
+    double v = 0;
+    need(get_real(nn[k], v), nn[k]);
+    n3[k] = (int)floor(v);
+    if (!(v >= least && v < 2147483648.0)) {
+      fprintf(stderr, refusal, nn[k]);
+      return 2;
+    }
+  }
+  return 0;
+}
+
+// --damping_dist --damping_mode --damping_Ne_h --damping_kT_eV --damping_tol (ours)
+static void read_damping_flags(srt_damping_params &dpar) {
+  get_int("damping_dist", dpar.dist);
+  get_int("damping_mode", dpar.mode);
+  get_real("damping_Ne_h", dpar.Ne_h);
+  double kTeV = 0;
+  if (get_real("damping_kT_eV", kTeV)) dpar.kT = kTeV * 1.60217646e-19;
+  get_real("damping_tol", dpar.tol);
+}
+
+// What srt_read_ray_file returns (n < 0: it failed, srt_last_error() says why) and the offsets of the packed layout, built from
+// `kept`: rows[offsets[n]][SRT_ROW] is the row set the post-processors take.  Freed on the way out.
+struct RayFile {
+  int32_t nspec = 0;
+  double qs[4], ms[4], *w0 = nullptr, *rows = nullptr;
+  int64_t n = -1, nrec = 0, *raynum = nullptr;
+  int32_t *stop = nullptr, *kept = nullptr;
+  std::vector<int64_t> offsets;
+  explicit RayFile(const std::string &path) {
+    n = srt_read_ray_file(path.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &rows);
+    offsets.assign(n > 0 ? (size_t)n + 1 : 1, 0);
+    for (int64_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + kept[i];
+  }
+  RayFile(const RayFile &) = delete;
+  RayFile &operator=(const RayFile &) = delete;
+  ~RayFile() { srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(rows); }
+};
+
+// A list-directed file of numbers, one record per line, `least` .. `most` (at most 5) numbers each: commas, tabs, CR and LF are
+// blanks, a d or D exponent reads as e, empty lines are skipped, values a line leaves out are 0.
+// -> 0; -1: the file cannot be opened; > 0: the number of the line that holds a bad token, too few numbers or one too many
+static int read_number_lines(const std::string &path, int least, int most, std::vector<std::array<double, 5>> &out) {
+  FILE *sf = fopen(path.c_str(), "r");
+  if (!sf) return -1;
+  char line[1024];
+  int lineno = 0, bad_line = 0;
+  while (!bad_line && fgets(line, sizeof line, sf)) {
+    ++lineno;
+    std::array<double, 5> v = {0, 0, 0, 0, 0};
+    int nv = 0;
+    for (char *q = line; *q; ++q)
+      if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
+      else if (*q == 'd' || *q == 'D') *q = 'e';
+    char *q = line;
+    bool bad = false;
+    for (;;) {
+      while (*q == ' ') ++q;
+      if (!*q) break;
+      char *end = nullptr;
+      const double x = strtod(q, &end);
+      if (end == q || nv == most) {
+        bad = true;
+        break;
+      }
+      v[nv++] = x;
+      q = end;
+    }
+    if (nv == 0 && !bad) continue; // an empty line
+    if (bad || nv < least) bad_line = lineno;
+    else out.push_back(v);
+  }
+  fclose(sf);
+  return bad_line;
+}
+
+// ---- the modes: each reads its own flags and returns the exit code ----
+// --grid2bin_in / --pts2bin_in: a model-3 grid or a model-4 sample file, text -> binary side-format (no GPU needed)
+static int mode_convert() {
+  std::string gin, gout, pin, pout;
+  if (getopt_named("grid2bin_in", gin)) {
+    need(getopt_named("grid2bin_out", gout), "grid2bin_out");
+    CHECK(srt_grid_file_convert(gin.c_str(), gout.c_str()));
     return 0;
   }
-  {
-    std::string gin, gout; // model-3 grid: text -> binary side-format (no GPU needed)
-    if (getopt_named("grid2bin_in", gin)) {
-      need(getopt_named("grid2bin_out", gout), "grid2bin_out");
-      CHECK(srt_grid_file_convert(gin.c_str(), gout.c_str()));
-      return 0;
-    }
+  need(getopt_named("pts2bin_in", pin), "pts2bin_in");
+  need(getopt_named("pts2bin_out", pout), "pts2bin_out");
+  CHECK(srt_points_file_convert(pin.c_str(), pout.c_str()));
+  return 0;
+}
+
+// the reference's gcpm_dens_model_buildgrid with the model of --modelnum in place of GCPM: same flags
+// (gcpm_dens_model_buildgrid.f95:42-160: --minx .. --maxz, --nx --ny --nz (reals, floored), --compder, --filename) and
+// the builder's exact text layout (:302-327, srt_grid_file_write); ours: --binary=1 (SRTGRID1), --device
+static int mode_buildgrid() {
+  std::string out;
+  need(getopt_named("filename", out), "filename");
+  double b[6], v = 0;
+  int n3[3] = {0, 0, 0}, compder = 0, device = 0, binary = 0;
+  if (int rc = need_grid(b, n3, 2.0, "raytracer: --%s must be >= 2 (the interpolated model needs two nodes per axis)\n")) return rc;
+  if (get_real("compder", v)) compder = (int)floor(v);
+  get_int("device", device);
+  get_int("binary", binary);
+  srt_model *m = nullptr;
+  double del = 0.0;
+  int rc = make_model(device, &m, &del);
+  if (rc) return rc;
+  const int nspec = srt_model_nspec(m);
+  const size_t nval = (size_t)n3[0] * n3[1] * n3[2] * nspec;
+  std::vector<double> F(nval), D(compder ? 7 * nval : 0);
+  CHECK(srt_build_grid(m, compder ? 1 : 0, n3[0], n3[1], n3[2], b, F.data(), compder ? D.data() : nullptr));
+  double qs[SRT_MAXSPEC], ms[SRT_MAXSPEC];
+  srt_model_species(m, qs, ms);
+  CHECK(srt_grid_file_write(out.c_str(), binary, nspec, n3[0], n3[1], n3[2], b, qs, ms, F.data(), compder ? D.data() : nullptr));
+  printf(" %d x %d x %d nodes, %d species%s\n", n3[0], n3[1], n3[2], nspec, compder ? ", 7 derivative blocks" : "");
+  srt_model_destroy(m);
+  return 0;
+}
+
+// the reference's gcpm_dens_model_buildgrid_random with the model of --modelnum in place of GCPM: same flags
+// (gcpm_dens_model_buildgrid_random.f95:56-90), --filename = output; ours: --seed, --binary=1
+static int mode_buildsamples() {
+  std::string out;
+  need(getopt_named("filename", out), "filename");
+  srt_sampler_params sp;
+  memset(&sp, 0, sizeof sp);
+  need_bounds(sp.bounds);
+  double v = 0;
+  if (get_real("n_zero_altitude", v)) sp.n_zero_altitude = (int64_t)floor(v);
+  if (get_real("n_iri_pad", v)) sp.n_iri_pad = (int64_t)floor(v);
+  if (get_real("n_initial_radial", v)) sp.n_initial_radial = (int64_t)floor(v);
+  if (get_real("n_initial_uniform", v)) sp.n_initial_uniform = (int64_t)floor(v);
+  sp.adaptive_nmax = 100000; // :92
+  if (get_real("adaptive_nmax", v)) sp.adaptive_nmax = (int64_t)floor(v);
+  get_real("initial_tol", sp.initial_tol);
+  get_int("max_recursion", sp.max_recursion);
+  if (get_real("seed", v)) sp.seed = (uint64_t)v;
+  int device = 0, binary = 0;
+  get_int("device", device);
+  get_int("binary", binary);
+  srt_model *m = nullptr;
+  double del = 0.0;
+  int rc = make_model(device, &m, &del);
+  if (rc) return rc;
+  int64_t n = 0, counts[6];
+  double *rec = nullptr;
+  CHECK(srt_build_samples(m, &sp, 0, nullptr, &n, &rec, counts));
+  double qs[SRT_MAXSPEC], ms[SRT_MAXSPEC];
+  srt_model_species(m, qs, ms);
+  CHECK(srt_points_file_write(out.c_str(), binary, srt_model_nspec(m), n, sp.bounds, qs, ms, rec));
+  printf(" %lld samples: %lld radial, %lld uniform, %lld adaptive, %lld zero-altitude, %lld ionosphere\n", (long long)n,
+         (long long)counts[1], (long long)counts[2], (long long)counts[3], (long long)counts[4], (long long)counts[5]);
+  srt_free(rec);
+  srt_model_destroy(m);
+  return 0;
+}
+
+// the reference's dumpmodel (fortran/dumpmodel.f95): funcPlasmaParams of the model of --modelnum at every node of a regular
+// grid, any axis of which may have one node.  Same flags (:167-213: --minx .. --maxz, --nx --ny --nz read as reals and
+// floored, --filename; the model's flags as make_model reads them) and the same text (:1284-1292, srt_dump_file_write).
+// --mag_coords (:1086-1091, :1238-1242) is read for modelnum 6 and 7 only, as there; absent = 0, the value the reference's
+// toolchain leaves in the unset variable.  Ours: --device, --timing=1.
+static int mode_dumpmodel() {
+  std::string out;
+  need(getopt_named("filename", out), "filename");
+  double b[6];
+  int n3[3] = {0, 0, 0}, device = 0, timing = 0, modelnum = 0, mag = 0;
+  if (int rc = need_grid(b, n3, 1.0, "raytracer: --%s must be >= 1 (one node = a slice: that axis sits at its minimum)\n")) return rc;
+  if ((double)n3[0] * n3[1] * n3[2] > 2147483647.0) {
+    fprintf(stderr, "raytracer: --nx x --ny x --nz is more than 2^31 - 1 nodes\n");
+    return 2;
   }
-  {
-    std::string pin, pout; // model-4 sample file: text -> binary side-format (no GPU needed)
-    if (getopt_named("pts2bin_in", pin)) {
-      need(getopt_named("pts2bin_out", pout), "pts2bin_out");
-      CHECK(srt_points_file_convert(pin.c_str(), pout.c_str()));
-      return 0;
-    }
+  get_int("device", device);
+  get_int("timing", timing);
+  get_int("modelnum", modelnum);
+  if (get_int("mag_coords", mag) && modelnum != 6 && modelnum != 7) {
+    fprintf(stderr, "raytracer: --mag_coords is read for --modelnum=6 and 7 only (as by the reference's dumpmodel); ignored for "
+                    "--modelnum=%d: the grid is in SM coordinates\n", modelnum);
+    mag = 0;
   }
-  {
-    // the reference's gcpm_dens_model_buildgrid with the model of --modelnum in place of GCPM: same flags
-    // (gcpm_dens_model_buildgrid.f95:42-160: --minx .. --maxz, --nx --ny --nz (reals, floored), --compder, --filename) and
-    // the builder's exact text layout (:302-327, srt_grid_file_write); ours: --binary=1 (SRTGRID1), --device
-    std::string flag;
-    if (getopt_named("buildgrid", flag) && flag != "0") {
-      std::string out;
-      need(getopt_named("filename", out), "filename");
-      double b[6], v = 0;
-      const char *bn[6] = {"minx", "maxx", "miny", "maxy", "minz", "maxz"};
-      for (int k = 0; k < 6; ++k) need(get_real(bn[k], b[k]), bn[k]);
-      int n3[3] = {0, 0, 0}, compder = 0, device = 0, binary = 0;
-      const char *nn[3] = {"nx", "ny", "nz"};
-      for (int k = 0; k < 3; ++k) {
-        need(get_real(nn[k], v), nn[k]);
-        n3[k] = (int)floor(v);
-        if (n3[k] < 2) {
-          fprintf(stderr, "raytracer: --%s must be >= 2 (the interpolated model needs two nodes per axis)\n", nn[k]);
-          return 2;
-        }
-      }
-      if (get_real("compder", v)) compder = (int)floor(v);
-      get_int("device", device);
-      get_int("binary", binary);
-      srt_model *m = nullptr;
-      double del = 0.0;
-      int rc = make_model(device, &m, &del);
-      if (rc) return rc;
-      const int nspec = srt_model_nspec(m);
-      const size_t nval = (size_t)n3[0] * n3[1] * n3[2] * nspec;
-      std::vector<double> F(nval), D(compder ? 7 * nval : 0);
-      CHECK(srt_build_grid(m, compder ? 1 : 0, n3[0], n3[1], n3[2], b, F.data(), compder ? D.data() : nullptr));
-      double qs[SRT_MAXSPEC], ms[SRT_MAXSPEC];
-      srt_model_species(m, qs, ms);
-      CHECK(srt_grid_file_write(out.c_str(), binary, nspec, n3[0], n3[1], n3[2], b, qs, ms, F.data(), compder ? D.data() : nullptr));
-      printf(" %d x %d x %d nodes, %d species%s\n", n3[0], n3[1], n3[2], nspec, compder ? ", 7 derivative blocks" : "");
-      srt_model_destroy(m);
-      return 0;
-    }
+  const double t0 = now_s();
+  srt_model *m = nullptr;
+  double del = 0.0;
+  int rc = make_model(device, &m, &del);
+  if (rc) return rc;
+  const double t1 = now_s();
+  const int nspec = srt_model_nspec(m);
+  std::vector<double> f((size_t)n3[0] * n3[1] * n3[2] * (4 * (size_t)nspec + 3));
+  CHECK(srt_dump_model(m, n3[0], n3[1], n3[2], b, mag, f.data()));
+  float kernel_ms = 0.f;
+  srt_last_kernel_ms(m, &kernel_ms);
+  const double t2 = now_s();
+  CHECK(srt_dump_file_write(out.c_str(), nspec, n3[0], n3[1], n3[2], b, f.data()));
+  const double t3 = now_s();
+  printf(" %d x %d x %d nodes, %d species, %s coordinates\n", n3[0], n3[1], n3[2], nspec, mag ? "MAG" : "SM");
+  if (timing)
+    printf(" timing: {\"model_s\": %.3f, \"dump_s\": %.3f, \"kernel_ms\": %.3f, \"write_s\": %.3f, \"wall_s\": %.3f}\n", t1 - t0, t2 - t1,
+           (double)kernel_ms, t3 - t2, t3 - t0);
+  srt_model_destroy(m);
+  return 0;
+}
+
+// ours: --damping_in=<existing .ray file> --damping_out=<file>: the MATLAB post-processor (matlab/damping/test_dampray.m)
+// on a file this program or the reference's driver wrote, without tracing anything
+static int mode_damping_in() {
+  std::string din, dout;
+  need(getopt_named("damping_in", din), "damping_in");
+  need(getopt_named("damping_out", dout), "damping_out");
+  srt_damping_params dpar;
+  memset(&dpar, 0, sizeof dpar);
+  read_damping_flags(dpar);
+  int device = 0;
+  get_int("device", device);
+  RayFile ray(din);
+  const int64_t n = ray.n;
+  if (n < 0) {
+    fprintf(stderr, "raytracer: %s\n", srt_last_error());
+    return 1;
   }
-  {
-    // the reference's gcpm_dens_model_buildgrid_random with the model of --modelnum in place of GCPM: same flags
-    // (gcpm_dens_model_buildgrid_random.f95:56-90), --filename = output; ours: --seed, --binary=1
-    std::string fname;
-    if (getopt_named("buildsamples", fname) && fname != "0") {
-      std::string out;
-      need(getopt_named("filename", out), "filename");
-      srt_sampler_params sp;
-      memset(&sp, 0, sizeof sp);
-      const char *bn[6] = {"minx", "maxx", "miny", "maxy", "minz", "maxz"};
-      for (int k = 0; k < 6; ++k) need(get_real(bn[k], sp.bounds[k]), bn[k]);
-      double v = 0;
-      if (get_real("n_zero_altitude", v)) sp.n_zero_altitude = (int64_t)floor(v);
-      if (get_real("n_iri_pad", v)) sp.n_iri_pad = (int64_t)floor(v);
-      if (get_real("n_initial_radial", v)) sp.n_initial_radial = (int64_t)floor(v);
-      if (get_real("n_initial_uniform", v)) sp.n_initial_uniform = (int64_t)floor(v);
-      sp.adaptive_nmax = 100000; // :92
-      if (get_real("adaptive_nmax", v)) sp.adaptive_nmax = (int64_t)floor(v);
-      get_real("initial_tol", sp.initial_tol);
-      get_int("max_recursion", sp.max_recursion);
-      if (get_real("seed", v)) sp.seed = (uint64_t)v;
-      int device = 0, binary = 0;
-      get_int("device", device);
-      get_int("binary", binary);
-      srt_model *m = nullptr;
-      double del = 0.0;
-      int rc = make_model(device, &m, &del);
-      if (rc) return rc;
-      int64_t n = 0, counts[6];
-      double *rec = nullptr;
-      CHECK(srt_build_samples(m, &sp, 0, nullptr, &n, &rec, counts));
-      double qs[SRT_MAXSPEC], ms[SRT_MAXSPEC];
-      srt_model_species(m, qs, ms);
-      CHECK(srt_points_file_write(out.c_str(), binary, srt_model_nspec(m), n, sp.bounds, qs, ms, rec));
-      printf(" %lld samples: %lld radial, %lld uniform, %lld adaptive, %lld zero-altitude, %lld ionosphere\n", (long long)n,
-             (long long)counts[1], (long long)counts[2], (long long)counts[3], (long long)counts[4], (long long)counts[5]);
-      srt_free(rec);
-      srt_model_destroy(m);
-      return 0;
-    }
+  FILE *f = fopen(dout.c_str(), "w");
+  if (!f) {
+    fprintf(stderr, "raytracer: cannot open %s\n", dout.c_str());
+    return 1;
   }
-  {
-    // the reference's dumpmodel (fortran/dumpmodel.f95): funcPlasmaParams of the model of --modelnum at every node of a regular
-    // grid, any axis of which may have one node.  Same flags (:167-213: --minx .. --maxz, --nx --ny --nz read as reals and
-    // floored, --filename; the model's flags as make_model reads them) and the same text (:1284-1292, srt_dump_file_write).
-    // --mag_coords (:1086-1091, :1238-1242) is read for modelnum 6 and 7 only, as there; absent = 0, the value the reference's
-    // toolchain leaves in the unset variable.  Ours: --device, --timing=1.
-    std::string flag;
-    if (getopt_named("dumpmodel", flag) && flag != "0") {
-      std::string out;
-      need(getopt_named("filename", out), "filename");
-      double b[6], v = 0;
-      const char *bn[6] = {"minx", "maxx", "miny", "maxy", "minz", "maxz"};
-      for (int k = 0; k < 6; ++k) need(get_real(bn[k], b[k]), bn[k]);
-      int n3[3] = {0, 0, 0}, device = 0, timing = 0, modelnum = 0, mag = 0;
-      const char *nn[3] = {"nx", "ny", "nz"};
-      for (int k = 0; k < 3; ++k) {
-        need(get_real(nn[k], v), nn[k]);
-        n3[k] = (int)floor(v);
-        if (!(v >= 1.0 && v < 2147483648.0)) {
-          fprintf(stderr, "raytracer: --%s must be >= 1 (one node = a slice: that axis sits at its minimum)\n", nn[k]);
-          return 2;
-        }
+  if (n > 0) {
+    CHECK(srt_init(device));
+    int slots = 1;
+    for (int64_t i = 0; i < n; ++i) slots = ray.kept[i] > slots ? ray.kept[i] : slots;
+    // the file's records are every row it kept: outputper = 1 with nrows = records of the ray
+    std::vector<double> rows((size_t)n * slots * SRT_ROW, 0.0), rate((size_t)n * slots), mag((size_t)n * slots);
+    std::vector<int32_t> flag((size_t)n * slots);
+    for (int64_t i = 0; i < n; ++i)
+      memcpy(rows.data() + (size_t)i * slots * SRT_ROW, ray.rows + (size_t)ray.offsets[i] * SRT_ROW, sizeof(double) * SRT_ROW * (size_t)ray.kept[i]);
+    CHECK(srt_damping(&dpar, ray.nspec, ray.qs, ray.ms, slots, 1, n, rows.data(), ray.kept, ray.w0, rate.data(), mag.data(), flag.data()));
+    for (int64_t i = 0; i < n; ++i)
+      for (int r = 0; r < ray.kept[i]; ++r) {
+        const size_t idx = (size_t)i * slots + r;
+        fprintf(f, "%10lld%10d%25.15E%25.15E%25.15E%10d\n", (long long)ray.raynum[i], r + 1, rows[idx * SRT_ROW], rate[idx], mag[idx], (int)flag[idx]);
       }
-      if ((double)n3[0] * n3[1] * n3[2] > 2147483647.0) {
-        fprintf(stderr, "raytracer: --nx x --ny x --nz is more than 2^31 - 1 nodes\n");
-        return 2;
-      }
-      get_int("device", device);
-      get_int("timing", timing);
-      get_int("modelnum", modelnum);
-      if (get_int("mag_coords", mag) && modelnum != 6 && modelnum != 7) {
-        fprintf(stderr, "raytracer: --mag_coords is read for --modelnum=6 and 7 only (as by the reference's dumpmodel); ignored for "
-                        "--modelnum=%d: the grid is in SM coordinates\n", modelnum);
-        mag = 0;
-      }
-      const double t0 = now_s();
-      srt_model *m = nullptr;
-      double del = 0.0;
-      int rc = make_model(device, &m, &del);
-      if (rc) return rc;
-      const double t1 = now_s();
-      const int nspec = srt_model_nspec(m);
-      std::vector<double> f((size_t)n3[0] * n3[1] * n3[2] * (4 * (size_t)nspec + 3));
-      CHECK(srt_dump_model(m, n3[0], n3[1], n3[2], b, mag, f.data()));
-      float kernel_ms = 0.f;
-      srt_last_kernel_ms(m, &kernel_ms);
-      const double t2 = now_s();
-      CHECK(srt_dump_file_write(out.c_str(), nspec, n3[0], n3[1], n3[2], b, f.data()));
-      const double t3 = now_s();
-      printf(" %d x %d x %d nodes, %d species, %s coordinates\n", n3[0], n3[1], n3[2], nspec, mag ? "MAG" : "SM");
-      if (timing)
-        printf(" timing: {\"model_s\": %.3f, \"dump_s\": %.3f, \"kernel_ms\": %.3f, \"write_s\": %.3f, \"wall_s\": %.3f}\n", t1 - t0, t2 - t1,
-               (double)kernel_ms, t3 - t2, t3 - t0);
-      srt_model_destroy(m);
-      return 0;
-    }
   }
-  {
-    // ours: --damping_in=<existing .ray file> --damping_out=<file>: the MATLAB post-processor (matlab/damping/test_dampray.m)
-    // on a file this program or the reference's driver wrote, without tracing anything
-    std::string din;
-    if (getopt_named("damping_in", din)) {
-      std::string dout;
-      need(getopt_named("damping_out", dout), "damping_out");
-      srt_damping_params dpar;
-      memset(&dpar, 0, sizeof dpar);
-      get_int("damping_dist", dpar.dist);
-      get_int("damping_mode", dpar.mode);
-      get_real("damping_Ne_h", dpar.Ne_h);
-      double kTeV = 0;
-      if (get_real("damping_kT_eV", kTeV)) dpar.kT = kTeV * 1.60217646e-19;
-      get_real("damping_tol", dpar.tol);
-      int device = 0;
-      get_int("device", device);
-      int32_t nspec = 0;
-      double qs[4], ms[4], *w0 = nullptr, *packed = nullptr;
-      int64_t nrec = 0, *raynum = nullptr;
-      int32_t *stop = nullptr, *kept = nullptr;
-      const int64_t n = srt_read_ray_file(din.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &packed);
-      if (n < 0) {
-        fprintf(stderr, "raytracer: %s\n", srt_last_error());
-        return 1;
-      }
-      FILE *f = fopen(dout.c_str(), "w");
-      if (!f) {
-        fprintf(stderr, "raytracer: cannot open %s\n", dout.c_str());
-        return 1;
-      }
-      if (n > 0) {
-        CHECK(srt_init(device));
-        int slots = 1;
-        for (int64_t i = 0; i < n; ++i) slots = kept[i] > slots ? kept[i] : slots;
-        // the file's records are every row it kept: outputper = 1 with nrows = records of the ray
-        std::vector<double> rows((size_t)n * slots * SRT_ROW, 0.0), rate((size_t)n * slots), mag((size_t)n * slots);
-        std::vector<int32_t> flag((size_t)n * slots);
-        int64_t off = 0;
-        for (int64_t i = 0; i < n; ++i) {
-          memcpy(rows.data() + (size_t)i * slots * SRT_ROW, packed + (size_t)off * SRT_ROW, sizeof(double) * SRT_ROW * (size_t)kept[i]);
-          off += kept[i];
-        }
-        CHECK(srt_damping(&dpar, nspec, qs, ms, slots, 1, n, rows.data(), kept, w0, rate.data(), mag.data(), flag.data()));
-        for (int64_t i = 0; i < n; ++i)
-          for (int r = 0; r < kept[i]; ++r) {
-            const size_t idx = (size_t)i * slots + r;
-            fprintf(f, "%10lld%10d%25.15E%25.15E%25.15E%10d\n", (long long)raynum[i], r + 1, rows[idx * SRT_ROW], rate[idx], mag[idx], (int)flag[idx]);
-          }
-      }
-      fclose(f);
-      printf(" %lld rays, %lld records\n", (long long)n, (long long)nrec);
-      srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed);
-      return 0;
-    }
+  fclose(f);
+  printf(" %lld rays, %lld records\n", (long long)n, (long long)ray.nrec);
+  return 0;
+}
+
+// ours: --approach_in=<existing .ray file> --approach_observers=<file> --approach_out=<file>: each ray's closest approach to
+// the observer points of the second file (include/srt.h), without tracing
+static int mode_approach() {
+  std::string ain, aobs, aout;
+  need(getopt_named("approach_in", ain), "approach_in");
+  need(getopt_named("approach_observers", aobs), "approach_observers");
+  need(getopt_named("approach_out", aout), "approach_out");
+  int device = 0;
+  get_int("device", device);
+  // one observer per line, list-directed as the surfaces file is: x y z radius
+  std::vector<std::array<double, 5>> lines;
+  const int bad = read_number_lines(aobs, 4, 4, lines);
+  if (bad < 0) {
+    fprintf(stderr, "raytracer: --approach_observers: cannot open %s\n", aobs.c_str());
+    return 1;
   }
-  {
-    // ours: --approach_in=<existing .ray file> --approach_observers=<file> --approach_out=<file>: each ray's closest approach to
-    // the observer points of the second file (include/srt.h), without tracing
-    std::string ain, aobs, aout;
-    const bool have_in = getopt_named("approach_in", ain), have_obs = getopt_named("approach_observers", aobs),
-               have_out = getopt_named("approach_out", aout);
-    if (have_in || have_obs || have_out) {
-      need(have_in, "approach_in");
-      need(have_obs, "approach_observers");
-      need(have_out, "approach_out");
-      int device = 0;
-      get_int("device", device);
-      // one observer per line, list-directed as the surfaces file is: x y z radius
-      std::vector<srt_observer> obs;
-      {
-        FILE *sf = fopen(aobs.c_str(), "r");
-        if (!sf) {
-          fprintf(stderr, "raytracer: --approach_observers: cannot open %s\n", aobs.c_str());
-          return 1;
-        }
-        char line[1024];
-        int lineno = 0;
-        while (fgets(line, sizeof line, sf)) {
-          ++lineno;
-          double v[4] = {0, 0, 0, 0};
-          int nv = 0;
-          for (char *q = line; *q; ++q)
-            if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
-            else if (*q == 'd' || *q == 'D') *q = 'e';
-          char *q = line;
-          bool bad = false;
-          for (;;) {
-            while (*q == ' ') ++q;
-            if (!*q) break;
-            char *end = nullptr;
-            const double x = strtod(q, &end);
-            if (end == q || nv == 4) {
-              bad = true;
-              break;
-            }
-            v[nv++] = x;
-            q = end;
-          }
-          if (nv == 0 && !bad) continue; // an empty line
-          if (bad || nv != 4) {
-            fclose(sf);
-            fprintf(stderr, "raytracer: --approach_observers: %s, line %d: expected `x y z radius` (four numbers)\n", aobs.c_str(), lineno);
-            return 1;
-          }
-          obs.push_back(srt_observer{{v[0], v[1], v[2]}, v[3]});
-        }
-        fclose(sf);
-        if (obs.empty() || obs.size() > (size_t)SRT_MAXOBS) {
-          fprintf(stderr, "raytracer: --approach_observers: %s holds %zu observers (1 .. %d are taken)\n", aobs.c_str(), obs.size(), SRT_MAXOBS);
-          return 1;
-        }
-      }
-      int32_t nspec = 0;
-      double qs[4], ms[4], *w0 = nullptr, *packed = nullptr;
-      int64_t nrec = 0, *raynum = nullptr;
-      int32_t *stop = nullptr, *kept = nullptr;
-      const int64_t n = srt_read_ray_file(ain.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &packed);
-      if (n < 0) {
-        fprintf(stderr, "raytracer: --approach_in: %s\n", srt_last_error());
-        return 1;
-      }
-      std::vector<int64_t> offsets((size_t)n + 1, 0);
-      for (int64_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + kept[i];
-      int64_t nev = 0;
-      double *ev = nullptr, *dist = nullptr;
-      int32_t *meta = nullptr;
-      if (nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
-        CHECK(srt_init(device));
-        CHECK(srt_approaches((int)obs.size(), obs.data(), n, offsets.data(), packed, &nev, &ev, &meta, &dist));
-      } else {
-        // the observers are still looked at: a bad one is refused whatever the file holds
-        int64_t zero[1] = {0};
-        const int rc = srt_approaches((int)obs.size(), obs.data(), 0, zero, nullptr, &nev, &ev, &meta, &dist);
-        if (rc == SRT_EINVAL) {
-          fprintf(stderr, "raytracer: %s\n", srt_last_error());
-          return 1;
-        }
-        nev = 0;
-      }
-      std::vector<int64_t> evray((size_t)nev);
-      for (int64_t e = 0; e < nev; ++e) evray[e] = raynum[meta[4 * e]];
-      CHECK(srt_approaches_file_write(aout.c_str(), nev, evray.data(), meta, dist, ev));
-      printf(" %lld rays, %lld records, %zu observers, %lld approaches\n", (long long)n, (long long)nrec, obs.size(), (long long)nev);
-      srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed), srt_free(ev), srt_free(meta), srt_free(dist);
-      return 0;
-    }
+  if (bad > 0) {
+    fprintf(stderr, "raytracer: --approach_observers: %s, line %d: expected `x y z radius` (four numbers)\n", aobs.c_str(), bad);
+    return 1;
   }
-  {
-    // ours: --crossings_in=<existing .ray file> --crossings_surfaces=<file> --crossings_out=<file>: where and when the rays of a
-    // file this program or the reference's driver wrote cross the surfaces of the second file (include/srt.h), without tracing
-    std::string cin_path, csurf, cout_path;
-    const bool have_in = getopt_named("crossings_in", cin_path), have_surf = getopt_named("crossings_surfaces", csurf),
-               have_out = getopt_named("crossings_out", cout_path);
-    if (have_in || have_surf || have_out) {
-      need(have_in, "crossings_in");
-      need(have_surf, "crossings_surfaces");
-      need(have_out, "crossings_out");
-      int device = 0;
-      get_int("device", device);
-      // one surface per line, list-directed: kind p0 p1 p2 p3; trailing values may be absent (0); a real kind is floored
-      std::vector<srt_surface> surf;
-      {
-        FILE *sf = fopen(csurf.c_str(), "r");
-        if (!sf) {
-          fprintf(stderr, "raytracer: --crossings_surfaces: cannot open %s\n", csurf.c_str());
-          return 1;
-        }
-        char line[1024];
-        int lineno = 0;
-        while (fgets(line, sizeof line, sf)) {
-          ++lineno;
-          double v[5] = {0, 0, 0, 0, 0};
-          int nv = 0;
-          for (char *q = line; *q; ++q)
-            if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
-            else if (*q == 'd' || *q == 'D') *q = 'e';
-          char *q = line;
-          bool bad = false;
-          for (;;) {
-            while (*q == ' ') ++q;
-            if (!*q) break;
-            char *end = nullptr;
-            const double x = strtod(q, &end);
-            if (end == q || nv == 5) {
-              bad = true;
-              break;
-            }
-            v[nv++] = x;
-            q = end;
-          }
-          if (bad) {
-            fclose(sf);
-            fprintf(stderr, "raytracer: --crossings_surfaces: %s, line %d: expected `kind p0 p1 p2 p3` (at most five numbers)\n", csurf.c_str(), lineno);
-            return 1;
-          }
-          if (nv == 0) continue; // an empty line
-          srt_surface s;
-          memset(&s, 0, sizeof s);
-          s.kind = (int32_t)floor(v[0]);
-          for (int k = 0; k < 4; ++k) s.p[k] = v[1 + k];
-          surf.push_back(s);
-        }
-        fclose(sf);
-        if (surf.empty() || surf.size() > SRT_MAXSURF) {
-          fprintf(stderr, "raytracer: --crossings_surfaces: %s holds %zu surfaces (1 .. %d are taken)\n", csurf.c_str(), surf.size(), SRT_MAXSURF);
-          return 1;
-        }
-      }
-      int32_t nspec = 0;
-      double qs[4], ms[4], *w0 = nullptr, *packed = nullptr;
-      int64_t nrec = 0, *raynum = nullptr;
-      int32_t *stop = nullptr, *kept = nullptr;
-      const int64_t n = srt_read_ray_file(cin_path.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &packed);
-      if (n < 0) {
-        fprintf(stderr, "raytracer: --crossings_in: %s\n", srt_last_error());
-        return 1;
-      }
-      std::vector<int64_t> offsets((size_t)n + 1, 0);
-      for (int64_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + kept[i];
-      int64_t nev = 0;
-      double *ev = nullptr;
-      int32_t *meta = nullptr;
-      if (nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
-        CHECK(srt_init(device));
-        CHECK(srt_crossings((int)surf.size(), surf.data(), n, offsets.data(), packed, &nev, &ev, &meta));
-      } else {
-        // the surfaces are still looked at: a bad one is refused whatever the file holds
-        int64_t zero[1] = {0};
-        const int rc = srt_crossings((int)surf.size(), surf.data(), 0, zero, nullptr, &nev, &ev, &meta);
-        if (rc == SRT_EINVAL) {
-          fprintf(stderr, "raytracer: %s\n", srt_last_error());
-          return 1;
-        }
-        nev = 0;
-      }
-      std::vector<int64_t> evray((size_t)nev);
-      for (int64_t e = 0; e < nev; ++e) evray[e] = raynum[meta[4 * e]];
-      CHECK(srt_crossings_file_write(cout_path.c_str(), nev, evray.data(), meta, ev));
-      printf(" %lld rays, %lld records, %zu surfaces, %lld crossings\n", (long long)n, (long long)nrec, surf.size(), (long long)nev);
-      srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed), srt_free(ev), srt_free(meta);
-      return 0;
-    }
+  std::vector<srt_observer> obs;
+  for (const auto &v : lines) obs.push_back(srt_observer{{v[0], v[1], v[2]}, v[3]});
+  if (obs.empty() || obs.size() > (size_t)SRT_MAXOBS) {
+    fprintf(stderr, "raytracer: --approach_observers: %s holds %zu observers (1 .. %d are taken)\n", aobs.c_str(), obs.size(), SRT_MAXOBS);
+    return 1;
   }
+  RayFile ray(ain);
+  if (ray.n < 0) {
+    fprintf(stderr, "raytracer: --approach_in: %s\n", srt_last_error());
+    return 1;
+  }
+  int64_t nev = 0;
+  double *ev = nullptr, *dist = nullptr;
+  int32_t *meta = nullptr;
+  if (ray.nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
+    CHECK(srt_init(device));
+    CHECK(srt_approaches((int)obs.size(), obs.data(), ray.n, ray.offsets.data(), ray.rows, &nev, &ev, &meta, &dist));
+  } else {
+    // the observers are still looked at: a bad one is refused whatever the file holds
+    int64_t zero[1] = {0};
+    const int rc = srt_approaches((int)obs.size(), obs.data(), 0, zero, nullptr, &nev, &ev, &meta, &dist);
+    if (rc == SRT_EINVAL) {
+      fprintf(stderr, "raytracer: %s\n", srt_last_error());
+      return 1;
+    }
+    nev = 0;
+  }
+  std::vector<int64_t> evray((size_t)nev);
+  for (int64_t e = 0; e < nev; ++e) evray[e] = ray.raynum[meta[4 * e]];
+  CHECK(srt_approaches_file_write(aout.c_str(), nev, evray.data(), meta, dist, ev));
+  printf(" %lld rays, %lld records, %zu observers, %lld approaches\n", (long long)ray.n, (long long)ray.nrec, obs.size(), (long long)nev);
+  srt_free(ev), srt_free(meta), srt_free(dist);
+  return 0;
+}
+
+// ours: --crossings_in=<existing .ray file> --crossings_surfaces=<file> --crossings_out=<file>: where and when the rays of a
+// file this program or the reference's driver wrote cross the surfaces of the second file (include/srt.h), without tracing
+static int mode_crossings() {
+  std::string cin_path, csurf, cout_path;
+  need(getopt_named("crossings_in", cin_path), "crossings_in");
+  need(getopt_named("crossings_surfaces", csurf), "crossings_surfaces");
+  need(getopt_named("crossings_out", cout_path), "crossings_out");
+  int device = 0;
+  get_int("device", device);
+  // one surface per line, list-directed: kind p0 p1 p2 p3; trailing values may be absent (0); a real kind is floored
+  std::vector<std::array<double, 5>> lines;
+  const int bad = read_number_lines(csurf, 1, 5, lines);
+  if (bad < 0) {
+    fprintf(stderr, "raytracer: --crossings_surfaces: cannot open %s\n", csurf.c_str());
+    return 1;
+  }
+  if (bad > 0) {
+    fprintf(stderr, "raytracer: --crossings_surfaces: %s, line %d: expected `kind p0 p1 p2 p3` (at most five numbers)\n", csurf.c_str(), bad);
+    return 1;
+  }
+  std::vector<srt_surface> surf;
+  for (const auto &v : lines) {
+    srt_surface s;
+    memset(&s, 0, sizeof s);
+    s.kind = (int32_t)floor(v[0]);
+    for (int k = 0; k < 4; ++k) s.p[k] = v[1 + k];
+    surf.push_back(s);
+  }
+  if (surf.empty() || surf.size() > SRT_MAXSURF) {
+    fprintf(stderr, "raytracer: --crossings_surfaces: %s holds %zu surfaces (1 .. %d are taken)\n", csurf.c_str(), surf.size(), SRT_MAXSURF);
+    return 1;
+  }
+  RayFile ray(cin_path);
+  if (ray.n < 0) {
+    fprintf(stderr, "raytracer: --crossings_in: %s\n", srt_last_error());
+    return 1;
+  }
+  int64_t nev = 0;
+  double *ev = nullptr;
+  int32_t *meta = nullptr;
+  if (ray.nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
+    CHECK(srt_init(device));
+    CHECK(srt_crossings((int)surf.size(), surf.data(), ray.n, ray.offsets.data(), ray.rows, &nev, &ev, &meta));
+  } else {
+    // the surfaces are still looked at: a bad one is refused whatever the file holds
+    int64_t zero[1] = {0};
+    const int rc = srt_crossings((int)surf.size(), surf.data(), 0, zero, nullptr, &nev, &ev, &meta);
+    if (rc == SRT_EINVAL) {
+      fprintf(stderr, "raytracer: %s\n", srt_last_error());
+      return 1;
+    }
+    nev = 0;
+  }
+  std::vector<int64_t> evray((size_t)nev);
+  for (int64_t e = 0; e < nev; ++e) evray[e] = ray.raynum[meta[4 * e]];
+  CHECK(srt_crossings_file_write(cout_path.c_str(), nev, evray.data(), meta, ev));
+  printf(" %lld rays, %lld records, %zu surfaces, %lld crossings\n", (long long)ray.n, (long long)ray.nrec, surf.size(), (long long)nev);
+  srt_free(ev), srt_free(meta);
+  return 0;
+}
+
+// ours: --bin_in=<existing .ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=2^-30]: the dwell-time
+// map of the rays of a file this program or the reference's driver wrote on the grid of the second file (include/srt.h),
+// without tracing.  What is wrong with the flags or the files is refused by name with exit code 2.
+static int mode_bin() {
+  std::string bin_path, baxes, bout_path;
+  need(getopt_named("bin_in", bin_path), "bin_in");
+  need(getopt_named("bin_axes", baxes), "bin_axes");
+  need(getopt_named("bin_out", bout_path), "bin_out");
+  int device = 0;
+  get_int("device", device);
+  srt_bin_params bp;
+  memset(&bp, 0, sizeof bp);
+  bp.nsub = 8;
+  bp.quantum = 9.313225746154785e-10; // 2^-30 s
+  get_int("bin_nsub", bp.nsub);
+  get_real("bin_quantum", bp.quantum);
+  // one axis per line: kind n e0 e1 .. en; the kind a number or a name; commas and d exponents are tolerated
+  std::vector<std::vector<double>> edges;
   {
-    // ours: --bin_in=<existing .ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=2^-30]: the dwell-time
-    // map of the rays of a file this program or the reference's driver wrote on the grid of the second file (include/srt.h),
-    // without tracing.  What is wrong with the flags or the files is refused by name with exit code 2.
-    std::string bin_path, baxes, bout_path;
-    const bool have_in = getopt_named("bin_in", bin_path), have_axes = getopt_named("bin_axes", baxes),
-               have_out = getopt_named("bin_out", bout_path);
-    if (have_in || have_axes || have_out) {
-      need(have_in, "bin_in");
-      need(have_axes, "bin_axes");
-      need(have_out, "bin_out");
-      int device = 0;
-      get_int("device", device);
-      srt_bin_params bp;
-      memset(&bp, 0, sizeof bp);
-      bp.nsub = 8;
-      bp.quantum = 9.313225746154785e-10; // 2^-30 s
-      get_int("bin_nsub", bp.nsub);
-      get_real("bin_quantum", bp.quantum);
-      // one axis per line: kind n e0 e1 .. en; the kind a number or a name; commas and d exponents are tolerated
-      std::vector<std::vector<double>> edges;
-      {
-        FILE *af = fopen(baxes.c_str(), "r");
-        if (!af) {
-          fprintf(stderr, "raytracer: --bin_axes: cannot open %s\n", baxes.c_str());
-          return 2;
-        }
-        static const char *names[8] = {"x", "y", "z", "r", "rho", "L", "sinlat", "mlt"};
-        std::vector<char> line(1 << 16);
-        int lineno = 0;
-        while (fgets(line.data(), (int)line.size(), af)) {
-          ++lineno;
-          for (char *q = line.data(); *q; ++q)
-            if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
-          char *q = line.data();
-          while (*q == ' ') ++q;
-          if (!*q) continue; // an empty line
-          const char *what = nullptr;
-          int kind = -1;
-          char *end = q;
-          while (*end && *end != ' ') ++end;
-          const std::string word(q, end);
-          for (int k = 0; k < 8; ++k)
-            if (word == names[k]) kind = k;
-          if (kind < 0) {
-            char *e2 = nullptr;
-            const double v = strtod(q, &e2);
-            if (e2 != end || !(v >= -1e9 && v <= 1e9)) what = "the kind is neither a number nor one of x y z r rho L sinlat mlt";
-            else kind = (int)floor(v);
-          }
-          std::vector<double> v;
-          for (q = end; !what;) {
-            while (*q == ' ') ++q;
-            if (!*q) break;
-            for (char *s = q; *s && *s != ' '; ++s)
-              if (*s == 'd' || *s == 'D') *s = 'e';
-            char *e2 = nullptr;
-            const double x = strtod(q, &e2);
-            if (e2 == q || (*e2 && *e2 != ' ')) what = "not a number";
-            v.push_back(x);
-            q = e2;
-          }
-          if (!what && (v.empty() || v[0] != floor(v[0]) || !(v[0] >= 1.0 && v[0] <= 1024.0))) what = "n is not a whole number of 1 .. 1024";
-          if (!what && v.size() != (size_t)v[0] + 2) what = "the line does not hold n + 1 edges";
-          if (!what && edges.size() == 3) what = "a fourth axis";
-          if (what) {
-            fclose(af);
-            fprintf(stderr, "raytracer: --bin_axes: %s, line %d: %s (expected `kind n e0 e1 .. en`)\n", baxes.c_str(), lineno, what);
-            return 2;
-          }
-          bp.axis[edges.size()].kind = kind;
-          bp.axis[edges.size()].n = (int32_t)v[0];
-          edges.emplace_back(v.begin() + 1, v.end());
-        }
+    FILE *af = fopen(baxes.c_str(), "r");
+    if (!af) {
+      fprintf(stderr, "raytracer: --bin_axes: cannot open %s\n", baxes.c_str());
+      return 2;
+    }
+    static const char *names[8] = {"x", "y", "z", "r", "rho", "L", "sinlat", "mlt"};
+    std::vector<char> line(1 << 16);
+    int lineno = 0;
+    while (fgets(line.data(), (int)line.size(), af)) {
+      ++lineno;
+      for (char *q = line.data(); *q; ++q)
+        if (*q == ',' || *q == '\t' || *q == '\r' || *q == '\n') *q = ' ';
+      char *q = line.data();
+      while (*q == ' ') ++q;
+      if (!*q) continue; // an empty line
+      const char *what = nullptr;
+      int kind = -1;
+      char *end = q;
+      while (*end && *end != ' ') ++end;
+      const std::string word(q, end);
+      for (int k = 0; k < 8; ++k)
+        if (word == names[k]) kind = k;
+      if (kind < 0) {
+        char *e2 = nullptr;
+        const double v = strtod(q, &e2);
+        if (e2 != end || !(v >= -1e9 && v <= 1e9)) what = "the kind is neither a number nor one of x y z r rho L sinlat mlt";
+        else kind = (int)floor(v);
+      }
+      std::vector<double> v;
+      for (q = end; !what;) {
+        while (*q == ' ') ++q;
+        if (!*q) break;
+        for (char *s = q; *s && *s != ' '; ++s)
+          if (*s == 'd' || *s == 'D') *s = 'e';
+        char *e2 = nullptr;
+        const double x = strtod(q, &e2);
+        if (e2 == q || (*e2 && *e2 != ' ')) what = "not a number";
+        v.push_back(x);
+        q = e2;
+      }
+      if (!what && (v.empty() || v[0] != floor(v[0]) || !(v[0] >= 1.0 && v[0] <= 1024.0))) what = "n is not a whole number of 1 .. 1024";
+      if (!what && v.size() != (size_t)v[0] + 2) what = "the line does not hold n + 1 edges";
+      if (!what && edges.size() == 3) what = "a fourth axis";
+      if (what) {
         fclose(af);
-        if (edges.empty()) {
-          fprintf(stderr, "raytracer: --bin_axes: %s holds no axis (1 .. 3 are taken)\n", baxes.c_str());
-          return 2;
-        }
-        bp.naxes = (int32_t)edges.size();
-        for (size_t a = 0; a < edges.size(); ++a) bp.axis[a].edges = edges[a].data();
-      }
-      int64_t ncells = 0;
-      if (srt_bin_cells(&bp, &ncells) != SRT_OK) { // --bin_nsub, --bin_quantum and the edges, by name
-        fprintf(stderr, "raytracer: --bin_axes / --bin_nsub / --bin_quantum: %s\n", srt_last_error());
+        fprintf(stderr, "raytracer: --bin_axes: %s, line %d: %s (expected `kind n e0 e1 .. en`)\n", baxes.c_str(), lineno, what);
         return 2;
       }
-      int32_t nspec = 0;
-      double qs[4], ms[4], *w0 = nullptr, *packed = nullptr;
-      int64_t nrec = 0, *raynum = nullptr;
-      int32_t *stop = nullptr, *kept = nullptr;
-      const int64_t n = srt_read_ray_file(bin_path.c_str(), &nspec, qs, ms, &nrec, &raynum, &stop, &kept, &w0, &packed);
-      if (n < 0) {
-        fprintf(stderr, "raytracer: --bin_in: %s\n", srt_last_error());
-        return 2;
-      }
-      std::vector<int64_t> offsets((size_t)n + 1, 0);
-      for (int64_t i = 0; i < n; ++i) offsets[i + 1] = offsets[i] + kept[i];
-      int64_t *ticks = nullptr, *hits = nullptr, counters[4] = {0, 0, 0, 0};
-      std::vector<int64_t> zeros;
-      if (nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
-        CHECK(srt_init(device));
-        CHECK(srt_bin_rays(&bp, n, offsets.data(), packed, nullptr, nullptr, &ticks, &hits, counters));
-      } else {
-        zeros.assign((size_t)ncells, 0);
-      }
-      CHECK(srt_bin_file_write(bout_path.c_str(), &bp, ticks ? ticks : zeros.data(), hits ? hits : zeros.data()));
-      printf(" %lld rays, %lld records, %lld cells: %lld intervals used, %lld skipped, %lld samples deposited, %lld outside\n",
-             (long long)n, (long long)nrec, (long long)ncells, (long long)counters[0], (long long)counters[1], (long long)counters[2],
-             (long long)counters[3]);
-      srt_free(raynum), srt_free(stop), srt_free(kept), srt_free(w0), srt_free(packed), srt_free(ticks), srt_free(hits);
-      return 0;
+      bp.axis[edges.size()].kind = kind;
+      bp.axis[edges.size()].n = (int32_t)v[0];
+      edges.emplace_back(v.begin() + 1, v.end());
     }
+    fclose(af);
+    if (edges.empty()) {
+      fprintf(stderr, "raytracer: --bin_axes: %s holds no axis (1 .. 3 are taken)\n", baxes.c_str());
+      return 2;
+    }
+    bp.naxes = (int32_t)edges.size();
+    for (size_t a = 0; a < edges.size(); ++a) bp.axis[a].edges = edges[a].data();
   }
+  int64_t ncells = 0;
+  if (srt_bin_cells(&bp, &ncells) != SRT_OK) { // --bin_nsub, --bin_quantum and the edges, by name
+    fprintf(stderr, "raytracer: --bin_axes / --bin_nsub / --bin_quantum: %s\n", srt_last_error());
+    return 2;
+  }
+  RayFile ray(bin_path);
+  if (ray.n < 0) {
+    fprintf(stderr, "raytracer: --bin_in: %s\n", srt_last_error());
+    return 2;
+  }
+  int64_t *ticks = nullptr, *hits = nullptr, counters[4] = {0, 0, 0, 0};
+  std::vector<int64_t> zeros;
+  if (ray.nrec >= 2) { // (fewer than two records hold no interval: nothing to ask a device for)
+    CHECK(srt_init(device));
+    CHECK(srt_bin_rays(&bp, ray.n, ray.offsets.data(), ray.rows, nullptr, nullptr, &ticks, &hits, counters));
+  } else {
+    zeros.assign((size_t)ncells, 0);
+  }
+  CHECK(srt_bin_file_write(bout_path.c_str(), &bp, ticks ? ticks : zeros.data(), hits ? hits : zeros.data()));
+  printf(" %lld rays, %lld records, %lld cells: %lld intervals used, %lld skipped, %lld samples deposited, %lld outside\n",
+         (long long)ray.n, (long long)ray.nrec, (long long)ncells, (long long)counters[0], (long long)counters[1], (long long)counters[2],
+         (long long)counters[3]);
+  srt_free(ticks), srt_free(hits);
+  return 0;
+}
+
+// the trace itself: the reference driver's run (raytracer_driver.f95) on the batched path
+static int mode_trace() {
   srt_params p;
   memset(&p, 0, sizeof p);
   int device = 0, chunk = 0;
@@ -822,14 +735,7 @@ int main(int argc, char **argv) {
   std::string damp_path;
   srt_damping_params dpar;
   memset(&dpar, 0, sizeof dpar);
-  if (getopt_named("damping_out", damp_path)) {
-    get_int("damping_dist", dpar.dist);
-    get_int("damping_mode", dpar.mode);
-    get_real("damping_Ne_h", dpar.Ne_h);
-    double kTeV = 0;
-    if (get_real("damping_kT_eV", kTeV)) dpar.kT = kTeV * 1.60217646e-19;
-    get_real("damping_tol", dpar.tol);
-  }
+  if (getopt_named("damping_out", damp_path)) read_damping_flags(dpar);
   // the reference opens the output with status="replace" even when there are no rays
   {
     FILE *f = fopen(out_path.c_str(), "w");
@@ -1071,4 +977,82 @@ int main(int argc, char **argv) {
   srt_free(dir0);
   srt_free(w0);
   return 0;
+}
+
+static bool have_flag(const char *name) {
+  std::string v;
+  return getopt_named(name, v);
+}
+// a mode that is switched on with --name=<anything but 0>
+static bool switched_on(const char *name) {
+  std::string v;
+  return getopt_named(name, v) && v != "0";
+}
+
+int main(int argc, char **argv) {
+  g_argc = argc;
+  g_argv = argv;
+  if (argc == 1) {
+    puts("Usage:\n  raytracer --param1=value1 --param2=value2 ...\n"
+         "  --dt0 --dtmax --tmax --root --fixedstep --maxerr --maxsteps --minalt\n"
+         "  --inputraysfile --outputfile --outputper\n"
+         "  --modelnum  (1) Ngo model  (3) interpolated model (gridded)  (4) interpolated model (scattered)\n"
+         "              (6) simplified GCPM (closed form)  (7) AT64ThCh (one field-line trace per evaluated point)\n"
+         "  model 1: --ngo_configfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1 --tsyganenko_Pdyn .. _W6\n"
+         "  model 3: --interp_interpfile --yearday --milliseconds_day --use_tsyganenko=0|1 --use_igrf=0|1\n"
+         "           [--interp_layout=expanded|nodes|auto: the table on the device; nodes = an eighth of the bytes, slower]\n"
+         "  model 4: model 3 flags + --scattered_interp_window_scale --scattered_interp_order\n"
+         "           --scattered_interp_exact --scattered_interp_local_window_scale\n"
+         "           [--scattered_interp_root_sample=N: record N of the file is the root of the reference's kd-tree (spacing 0)]\n"
+         "  model 6: --kp --yearday --milliseconds_day [--fixed_MLT=1 --MLT=<hours>] --use_tsyganenko=0|1 --use_igrf=0|1\n"
+         "           --tsyganenko_Pdyn .. _W6  (--ngo_configfile is accepted and ignored, as by the reference's driver)\n"
+         "  model 7: --gcpm_kp=<integer> --yearday --milliseconds_day --tsyganenko_Pdyn .. _W6 (all ten, also with\n"
+         "           --use_tsyganenko=0: the model's field-line trace always runs through T04_s + IGRF)\n"
+         "           --use_tsyganenko=0|1 --use_igrf=0|1 [--igrf_coeffs=<table>]\n"
+         "  extra:   --device=N | --devices=0,1,..  --chunk_rays=N  --ray_order=0|1  --timing=1 (wall clock per phase)\n"
+         "           --segment_rows=N: trace in segments of N kept rows per ray and launch (rays are paused and resumed; device\n"
+         "             memory for chunk_rays * N rows instead of chunk_rays * maxsteps / outputper, the same .ray file; chunks of\n"
+         "             262144 rays unless --chunk_rays says otherwise; not together with --damping_out).  0 / absent: one launch per chunk\n"
+         "           --first_attempt_policy=1|0: error estimate of a ray's first adaptive attempt, where the reference reads an\n"
+         "             unset variable: 1 (default) = from the k term alone, as the reference's gfortran build behaves;\n"
+         "             0 = NaN => accepted at dt0, dt not grown, as a flang build behaves (the goldens of this repository)\n"
+         "  tools:   --grid2bin_in=<text grid> --grid2bin_out=<binary grid>   (convert and exit; --interp_interpfile\n"
+         "           accepts either form);  --pts2bin_in / --pts2bin_out: the same for model-4 sample files\n"
+         "           --buildgrid=1 --filename=<out> --minx .. --maxz --nx --ny --nz --compder=0|1 (the reference's regular grid\n"
+         "           builder gcpm_dens_model_buildgrid with the model of --modelnum in place of GCPM; --binary=1)\n"
+         "           --buildsamples=1 --filename=<out> --minx .. --maxz --n_initial_uniform ... (the reference's random grid\n"
+         "           builder with the model of --modelnum in place of GCPM; --seed, --binary=1)\n"
+         "           --dumpmodel=1 --filename=<out> --minx .. --maxz --nx --ny --nz (the reference's dumpmodel: qs, Ns, ms, nus, B0\n"
+         "           of the model of --modelnum at every node; an axis may have one node; --mag_coords=1 with model 6 or 7: the\n"
+         "           grid is in MAG coordinates)\n"
+         "           --damping_out=<file>: hot-plasma damping along the kept rows (raynum, row, t, rate, magnitude, flag);\n"
+         "           with --damping_in=<.ray file> instead of tracing: along the records of an existing file\n"
+         "           --crossings_in=<.ray file> --crossings_surfaces=<file> --crossings_out=<file> [--device=N]: where and when the\n"
+         "           rays of an existing file cross surfaces, located on the cubic Hermite curve through consecutive records;\n"
+         "           the surfaces file holds one `kind p0 p1 p2 p3` per line (0 sphere: radius in m; 1 L-shell: L; 2 magnetic\n"
+         "           latitude: radians; 3 plane: normal and offset; trailing values may be absent); one record per crossing:\n"
+         "           raynum, surface, interval, direction (4 i10), then t, pos, vprel, vgrel, n, B0, Ns (20 es24.15e3)\n"
+         "           --approach_in=<.ray file> --approach_observers=<file> --approach_out=<file> [--device=N]: each ray's closest\n"
+         "           approach to observer points, located on the cubic Hermite curve through consecutive records; the observers\n"
+         "           file holds one `x y z radius` per line (SM metres; an approach is reported when it comes within the radius);\n"
+         "           one record per event: raynum, observer, interval, 0 (4 i10), then the distance and t, pos, vprel, vgrel, n,\n"
+         "           B0, Ns (21 es24.15e3)\n"
+         "           --bin_in=<.ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=9.313225746154785e-10]\n"
+         "           [--device=N]: the dwell-time map of the rays of an existing file: every interval of consecutive records is cut\n"
+         "           into bin_nsub pieces on the cubic Hermite curve, each deposits its duration into the cell of its midpoint, in\n"
+         "           whole ticks of bin_quantum seconds; the axes file holds one axis per line, `kind n e0 e1 .. en` (kind 0 .. 7\n"
+         "           or x y z r rho L sinlat mlt; metres, L, sine of the magnetic latitude, hours; 1 .. 3 axes of 1 .. 1024 cells);\n"
+         "           the output holds the grid, then per cell seconds (es24.15e3) and samples (i20)");
+    return 0;
+  }
+  if (have_flag("grid2bin_in") || have_flag("pts2bin_in")) return mode_convert();
+  if (switched_on("buildgrid")) return mode_buildgrid();
+  if (switched_on("buildsamples")) return mode_buildsamples();
+  if (switched_on("dumpmodel")) return mode_dumpmodel();
+  if (have_flag("damping_in")) return mode_damping_in();
+  // (one flag of a post-processor's three selects it; the mode then names the ones that are missing)
+  if (have_flag("approach_in") || have_flag("approach_observers") || have_flag("approach_out")) return mode_approach();
+  if (have_flag("crossings_in") || have_flag("crossings_surfaces") || have_flag("crossings_out")) return mode_crossings();
+  if (have_flag("bin_in") || have_flag("bin_axes") || have_flag("bin_out")) return mode_bin();
+  return mode_trace();
 }

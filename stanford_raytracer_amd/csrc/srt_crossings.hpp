@@ -1,6 +1,6 @@
 // srt_crossings.hpp -- where and when a traced ray crosses a surface (include/srt.h, "surface crossings"): the surfaces' g(x),
-// the cubic Hermite curve through two consecutive kept rows (end slopes C * vgrel, the right-hand side of the position equation
-// the rows already carry), the bisection that locates a sign change of g on it, and the two passes over packed rows.
+// the bisection that locates a sign change of g on the cubic Hermite curve through two consecutive kept rows (srt_rows.hpp),
+// and the two passes over packed rows.
 //
 // Two halves.  The POINT FUNCTIONS are __host__ __device__ and spell out every operation with contraction off (as
 // srt_xform.hpp does), so that a host build (tests/native/crossings_host.cpp) and the device give the same bits wherever sqrt
@@ -10,29 +10,13 @@
 //
 // Compiles for the device (hipcc) and for the host.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include "../../include/srt.h"
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define CX_HD __host__ __device__
-#else
-#define CX_HD
-#endif
-#if defined(__clang__)
-#define CX_NOCONTRACT _Pragma("clang fp contract(off)")
-#else
-#define CX_NOCONTRACT // (g++: built with -ffp-contract=off)
-#endif
+#include "srt_rows.hpp"
 
 namespace srt {
 namespace crossings {
 
-constexpr int BISECTIONS = 52; // the bracket [0, 1] halves to 2^-52: sigma* is within 2^-50 of the sign change, with room
-constexpr double EARTH_RADIUS = 6371.2e3; // constants.f95:8
+// C as prepare() puts it into Surfaces::C, under the name callers of this header have always had for it
+using rows::light_speed;
 
 // the surfaces as the passes read them: a kind-1 p[0] is L * R_E, a kind-2 p[0] the sine of the latitude (both taken once, on
 // the host), C the speed of light as the library's models compute it
@@ -41,13 +25,6 @@ struct Surfaces {
   double C;
   srt_surface s[SRT_MAXSURF];
 };
-
-inline double light_speed() {
-  CX_NOCONTRACT
-  const double EPS0 = 8.854187817e-12, PI = 3.141592653589793238462643; // constants.f95:4-5
-  const double MU0 = PI * 4e-7;                                        // constants.f95:6
-  return sqrt(1.0 / EPS0 / MU0);                                       // constants.f95:7
-}
 
 // Host: the refusals of include/srt.h, by name.  0 = fine and *out is ready; otherwise `why` says what is wrong.
 inline int prepare(int nsurf, const srt_surface *in, Surfaces *out, char *why, size_t whylen) {
@@ -87,7 +64,7 @@ inline int prepare(int nsurf, const srt_surface *in, Surfaces *out, char *why, s
         snprintf(why, whylen, "surface %d: L = %g is not > 0", i, s.p[0]);
         return -1;
       }
-      o.p[0] = s.p[0] * EARTH_RADIUS;
+      o.p[0] = s.p[0] * rows::EARTH_RADIUS;
     } else if (s.kind == 2) {
       if (!(fabs(s.p[0]) < 1.5707963267948966)) {
         snprintf(why, whylen, "surface %d: |latitude| = %g rad is not below pi/2", i, fabs(s.p[0]));
@@ -107,8 +84,8 @@ inline int prepare(int nsurf, const srt_surface *in, Surfaces *out, char *why, s
 }
 
 // g(x) of a prepared surface, x in SM metres
-CX_HD inline double surface_g(const srt_surface &s, const double x[3]) {
-  CX_NOCONTRACT
+ROWS_HD inline double surface_g(const srt_surface &s, const double x[3]) {
+  ROWS_NOCONTRACT
   if (s.kind == 3) return s.p[0] * x[0] + s.p[1] * x[1] + s.p[2] * x[2] - s.p[3];
   const double rho2 = x[0] * x[0] + x[1] * x[1];
   const double r2 = rho2 + x[2] * x[2];
@@ -118,17 +95,9 @@ CX_HD inline double surface_g(const srt_surface &s, const double x[3]) {
   return x[2] - r * s.p[0];
 }
 
-// can the interval between two kept rows hold events at all: t, pos and vgrel finite at both ends, and t1 != t0
-CX_HD inline bool interval_usable(const double *r0, const double *r1) {
-  bool ok = __builtin_isfinite(r0[0]) && __builtin_isfinite(r1[0]) && r1[0] != r0[0];
-  for (int c = 0; c < 3; ++c)
-    ok = ok && __builtin_isfinite(r0[1 + c]) && __builtin_isfinite(r1[1 + c]) && __builtin_isfinite(r0[7 + c]) && __builtin_isfinite(r1[7 + c]);
-  return ok;
-}
-
 // bit s: (g_i < 0) != (g_{i+1} < 0) for surface s -- a row exactly on the surface gives one event per pass, not two
-CX_HD inline uint32_t interval_mask(const Surfaces &S, const double *r0, const double *r1) {
-  if (!interval_usable(r0, r1)) return 0u;
+ROWS_HD inline uint32_t interval_mask(const Surfaces &S, const double *r0, const double *r1) {
+  if (!rows::interval_usable(r0, r1)) return 0u;
   uint32_t m = 0u;
   for (int s = 0; s < S.n; ++s) {
     const bool n0 = surface_g(S.s[s], r0 + 1) < 0.0, n1 = surface_g(S.s[s], r1 + 1) < 0.0;
@@ -137,91 +106,46 @@ CX_HD inline uint32_t interval_mask(const Surfaces &S, const double *r0, const d
   return m;
 }
 
-// The cubic Hermite curve in its Delta form (the basis-function form cancels at 1e7 m):
-//   p(sigma) = p0 + sigma m0 + sigma^2 (3 D - 2 m0 - m1) + sigma^3 (m0 + m1 - 2 D),  D = p1 - p0,  m = C vgrel h
-struct Interval {
-  double t0, h;
-  double p0[3], m0[3], c2[3], c3[3];
-};
-CX_HD inline void interval_setup(const double *r0, const double *r1, double C, Interval &iv) {
-  CX_NOCONTRACT
-  iv.t0 = r0[0];
-  iv.h = r1[0] - r0[0];
-  for (int c = 0; c < 3; ++c) {
-    const double d = r1[1 + c] - r0[1 + c];
-    const double m0 = C * r0[7 + c] * iv.h, m1 = C * r1[7 + c] * iv.h;
-    iv.p0[c] = r0[1 + c];
-    iv.m0[c] = m0;
-    iv.c2[c] = 3.0 * d - 2.0 * m0 - m1;
-    iv.c3[c] = m0 + m1 - 2.0 * d;
-  }
-}
-CX_HD inline void hermite(const Interval &iv, double sigma, double x[3]) {
-  CX_NOCONTRACT
-  for (int c = 0; c < 3; ++c) x[c] = iv.p0[c] + sigma * (iv.m0[c] + sigma * (iv.c2[c] + sigma * iv.c3[c]));
-}
-
 // sigma*: BISECTIONS halvings of [0, 1], keeping the rows' end signs either side (neg0 = g_i < 0).  Returned is the end of the
 // last bracket on which g >= 0, so that a row exactly on the surface is found at sigma = 1 or 0 exactly.
-CX_HD inline double locate(const srt_surface &s, const Interval &iv, bool neg0) {
-  CX_NOCONTRACT
+ROWS_HD inline double locate(const srt_surface &s, const rows::Interval &iv, bool neg0) {
+  ROWS_NOCONTRACT
   double lo = 0.0, hi = 1.0;
-  for (int it = 0; it < BISECTIONS; ++it) {
+  for (int it = 0; it < rows::BISECTIONS; ++it) {
     const double mid = 0.5 * (lo + hi);
     double x[3];
-    hermite(iv, mid, x);
+    rows::hermite(iv, mid, x);
     if ((surface_g(s, x) < 0.0) == neg0) lo = mid;
     else hi = mid;
   }
   return neg0 ? hi : lo;
 }
 
-// the event as a row of the kept-row layout: t and pos on the curve, columns 4 .. 19 linear in sigma
-CX_HD inline void event_row(const Interval &iv, const double *r0, const double *r1, double sigma, double *out) {
-  CX_NOCONTRACT
-  out[0] = iv.t0 + sigma * iv.h;
-  hermite(iv, sigma, out + 1);
-  for (int c = 4; c < SRT_ROW; ++c) out[c] = r0[c] + sigma * (r1[c] - r0[c]);
-}
-
-// the ray of packed row j: the last r in [0, nrays) with offsets[r] <= j (empty rays have offsets[r] == offsets[r + 1] and
-// are never the answer for a row that exists); -1 if offsets[0] > j
-CX_HD inline long long ray_of_row(const long long *offsets, long long nrays, long long j) {
-  long long lo = 0, hi = nrays;
-  while (lo < hi) {
-    const long long mid = lo + (hi - lo) / 2;
-    if (offsets[mid] <= j) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo - 1;
-}
-
 // the mask of packed row j: of the interval (j, j + 1) when both rows belong to one ray.  The geometry is looked at first: most
 // rows have no sign change, and only those that have one pay for the search in offsets.
-CX_HD inline uint32_t row_mask(const Surfaces &S, long long nrays, const long long *offsets, long long total, const double *rows,
-                               long long j) {
+ROWS_HD inline uint32_t row_mask(const Surfaces &S, long long nrays, const long long *offsets, long long total, const double *rows,
+                                 long long j) {
   if (j + 1 >= total) return 0u;
   const uint32_t m = interval_mask(S, rows + j * SRT_ROW, rows + (j + 1) * SRT_ROW);
   if (!m) return 0u;
-  const long long r = ray_of_row(offsets, nrays, j);
-  if (r < 0 || j + 1 >= offsets[r + 1]) return 0u;
+  if (rows::interval_ray(offsets, nrays, j) < 0) return 0u;
   return m;
 }
 
 // the events of packed row j, event number e0 onwards; events numbered >= capacity are left out
-CX_HD inline void row_events(const Surfaces &S, long long nrays, const long long *offsets, const double *rows, long long j, uint32_t m,
-                             long long e0, long long capacity, double *ev_rows, int32_t *ev_meta) {
-  const long long r = ray_of_row(offsets, nrays, j);
+ROWS_HD inline void row_events(const Surfaces &S, long long nrays, const long long *offsets, const double *rows, long long j, uint32_t m,
+                               long long e0, long long capacity, double *ev_rows, int32_t *ev_meta) {
+  const long long r = rows::ray_of_row(offsets, nrays, j);
   if (r < 0) return;
   const double *r0 = rows + j * SRT_ROW, *r1 = r0 + SRT_ROW;
-  Interval iv;
-  interval_setup(r0, r1, S.C, iv);
+  rows::Interval iv;
+  rows::interval_setup(r0, r1, S.C, iv);
   long long e = e0;
   for (int s = 0; s < S.n && e < capacity; ++s) {
     if (!(m >> s & 1u)) continue;
     const bool neg0 = surface_g(S.s[s], r0 + 1) < 0.0;
     const double sigma = locate(S.s[s], iv, neg0);
-    event_row(iv, r0, r1, sigma, ev_rows + e * SRT_ROW);
+    rows::event_row(iv, r0, r1, sigma, ev_rows + e * SRT_ROW);
     int32_t *q = ev_meta + e * 4;
     q[0] = (int32_t)r;
     q[1] = s;

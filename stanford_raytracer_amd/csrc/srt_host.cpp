@@ -8,7 +8,6 @@
 
 #include "srt_host.hpp"
 #include "srt_xform.hpp"
-#define SRT_CROSSINGS_NO_KERNELS
 #define SRT_BINNING_NO_KERNELS
 #include "srt_binning.hpp"
 
@@ -854,20 +853,18 @@ extern "C" int srt_write_ray_file_packed(const char *path, int append, int64_t r
   return write_ray_records(path, append, raynum0, nrays, nspec, qs, ms, w0, rows, stopcond, prefix, 0, 1);
 }
 
-// ---- crossings file: one record per event, (4 i10, 20 es24.15e3): raynum, surface + 1, interval + 1, direction, the row ----
-extern "C" int srt_crossings_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
-                                        const double *event_rows) {
-  if (!path || nevents < 0 || (nevents > 0 && (!raynum || !event_meta || !event_rows)))
-    return srt_set_error(SRT_EINVAL, "srt_crossings_file_write: null argument");
+// ---- event files: one record per event, (4 i10, then es24.15e3 fields): raynum, index + 1, interval + 1, meta[3], [distance,] the row ----
+static int write_event_records(const char *who, const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
+                               const double *event_dist, const double *event_rows) {
   for (int64_t e = 0; e < nevents; ++e)
     if (raynum[e] < 0 || raynum[e] > 9999999999ll)
-      return srt_set_error(SRT_EINVAL, "srt_crossings_file_write: ray number %lld of event %lld does not fit the record's i10 field",
+      return srt_set_error(SRT_EINVAL, "%s: ray number %lld of event %lld does not fit the record's i10 field", who,
                            (long long)raynum[e], (long long)e);
   FILE *fp = fopen(path, "w");
   if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
   std::vector<char> big(1 << 22);
   setvbuf(fp, big.data(), _IOFBF, big.size());
-  const size_t L = 40 + (size_t)SRT_ROW * 24 + 1;
+  const size_t L = 40 + (size_t)(SRT_ROW + (event_dist ? 1 : 0)) * 24 + 1;
   std::vector<char> rec(L + 8);
   for (int64_t e = 0; e < nevents; ++e) {
     const int32_t *m = event_meta + 4 * e;
@@ -875,6 +872,10 @@ extern "C" int srt_crossings_file_write(const char *path, int64_t nevents, const
     snprintf(head, sizeof head, "%10lld%10d%10d%10d", (long long)raynum[e], (int)m[1] + 1, (int)m[2] + 1, (int)m[3]);
     memcpy(rec.data(), head, 40);
     char *q = rec.data() + 40;
+    if (event_dist) {
+      put_es24(event_dist[e], q);
+      q += 24;
+    }
     for (int c = 0; c < SRT_ROW; ++c, q += 24) put_es24(event_rows[(size_t)e * SRT_ROW + c], q);
     *q = '\n';
     fwrite(rec.data(), 1, L, fp);
@@ -883,35 +884,20 @@ extern "C" int srt_crossings_file_write(const char *path, int64_t nevents, const
   return SRT_OK;
 }
 
-// ---- approaches file: one record per event, (4 i10, 21 es24.15e3): raynum, observer + 1, interval + 1, 0, distance, the row ----
+// crossings file: (4 i10, 20 es24.15e3): raynum, surface + 1, interval + 1, direction, the row
+extern "C" int srt_crossings_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
+                                        const double *event_rows) {
+  if (!path || nevents < 0 || (nevents > 0 && (!raynum || !event_meta || !event_rows)))
+    return srt_set_error(SRT_EINVAL, "srt_crossings_file_write: null argument");
+  return write_event_records("srt_crossings_file_write", path, nevents, raynum, event_meta, nullptr, event_rows);
+}
+
+// approaches file: (4 i10, 21 es24.15e3): raynum, observer + 1, interval + 1, 0, distance, the row
 extern "C" int srt_approaches_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
                                          const double *event_dist, const double *event_rows) {
   if (!path || nevents < 0 || (nevents > 0 && (!raynum || !event_meta || !event_dist || !event_rows)))
     return srt_set_error(SRT_EINVAL, "srt_approaches_file_write: null argument");
-  for (int64_t e = 0; e < nevents; ++e)
-    if (raynum[e] < 0 || raynum[e] > 9999999999ll)
-      return srt_set_error(SRT_EINVAL, "srt_approaches_file_write: ray number %lld of event %lld does not fit the record's i10 field",
-                           (long long)raynum[e], (long long)e);
-  FILE *fp = fopen(path, "w");
-  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
-  std::vector<char> big(1 << 22);
-  setvbuf(fp, big.data(), _IOFBF, big.size());
-  const size_t L = 40 + (size_t)(SRT_ROW + 1) * 24 + 1;
-  std::vector<char> rec(L + 8);
-  for (int64_t e = 0; e < nevents; ++e) {
-    const int32_t *m = event_meta + 4 * e;
-    char head[48];
-    snprintf(head, sizeof head, "%10lld%10d%10d%10d", (long long)raynum[e], (int)m[1] + 1, (int)m[2] + 1, (int)m[3]);
-    memcpy(rec.data(), head, 40);
-    char *q = rec.data() + 40;
-    put_es24(event_dist[e], q);
-    q += 24;
-    for (int c = 0; c < SRT_ROW; ++c, q += 24) put_es24(event_rows[(size_t)e * SRT_ROW + c], q);
-    *q = '\n';
-    fwrite(rec.data(), 1, L, fp);
-  }
-  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
-  return SRT_OK;
+  return write_event_records("srt_approaches_file_write", path, nevents, raynum, event_meta, event_dist, event_rows);
 }
 
 // ---- bin file: a map of srt_bin_rays as text (include/srt.h) ----

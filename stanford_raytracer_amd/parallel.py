@@ -90,39 +90,47 @@ def pack_rows_device(rows, nrows, outputper, stream=None, slot=None):
     return packed, offsets
 
 
+def _events_device(call, offsets, capacity, stream, with_dist):
+    """What crossings_device and approaches_device share.  call(ev, meta, dist, capacity, count, stream) is the library's device
+    entry point on addresses (None = null) -> (event_rows, meta, dist, count); dist is None unless with_dist.  capacity=None:
+    a count-only call, one wait for the GPU, then room for exactly the events there are (none: no second call); capacity=0:
+    count only."""
+    import torch
+
+    from . import api
+
+    dev = offsets.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if not capacity:
+        api._check(call(None, None, None, 0, count.data_ptr(), st.cuda_stream))
+        if capacity is None:
+            st.synchronize()
+            capacity = int(count.item())
+        if capacity == 0:
+            return None, None, None, count
+    ev = torch.zeros((capacity, ROW), dtype=torch.float64, device=dev)
+    meta = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
+    dist = torch.zeros(capacity, dtype=torch.float64, device=dev) if with_dist else None
+    api._check(call(ev.data_ptr(), meta.data_ptr(), dist.data_ptr() if with_dist else None, capacity, count.data_ptr(),
+                    st.cuda_stream))
+    return ev, meta, dist, count
+
+
 def approaches_device(packed, offsets, observers, capacity=None, stream=None):
     """srt_approaches_device on torch CUDA tensors (packed[>= offsets[n], 20], offsets[n + 1] as pack_rows_device returns them;
     observers as api.observer_array takes them) -> (event_rows[capacity, 20], meta[capacity, 4] int32, dist[capacity],
     count[1] int64), all on the device; the first min(count, capacity) events are valid.  capacity=None: a count-only call first,
     then room for exactly the events there are (one wait for the GPU); capacity=0: count only, the other three are None."""
-    import ctypes as C
-
-    import torch
-
     from . import api
 
     arr, no = api.observer_array(observers)
     n = offsets.shape[0] - 1
-    dev = offsets.device
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    if capacity is None:
-        api._check(api.lib().srt_approaches_device(no, arr, n, offsets.data_ptr(), packed.data_ptr(), None, None, None, 0,
-                                                   count.data_ptr(), st.cuda_stream))
-        st.synchronize()
-        capacity = int(count.item())
-        if capacity == 0:
-            return None, None, None, count
-    if capacity == 0:
-        api._check(api.lib().srt_approaches_device(no, arr, n, offsets.data_ptr(), packed.data_ptr(), None, None, None, 0,
-                                                   count.data_ptr(), st.cuda_stream))
-        return None, None, None, count
-    ev = torch.zeros((capacity, ROW), dtype=torch.float64, device=dev)
-    meta = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
-    dist = torch.zeros(capacity, dtype=torch.float64, device=dev)
-    api._check(api.lib().srt_approaches_device(no, arr, n, offsets.data_ptr(), packed.data_ptr(), ev.data_ptr(), meta.data_ptr(),
-                                               dist.data_ptr(), C.c_int64(capacity), count.data_ptr(), st.cuda_stream))
-    return ev, meta, dist, count
+
+    def call(ev, meta, dist, cap, count, st):
+        return api.lib().srt_approaches_device(no, arr, n, offsets.data_ptr(), packed.data_ptr(), ev, meta, dist, cap, count, st)
+
+    return _events_device(call, offsets, capacity, stream, True)
 
 
 def crossings_device(packed, offsets, surfaces, capacity=None, stream=None):
@@ -130,30 +138,15 @@ def crossings_device(packed, offsets, surfaces, capacity=None, stream=None):
     -> (event_rows[capacity, 20], meta[capacity, 4] int32, count[1] int64), all on the device; the first min(count, capacity)
     events are valid.  capacity=None: a count-only call first, then room for exactly the events there are (one wait for the
     GPU); capacity=0: count only, event_rows and meta are None."""
-    import ctypes as C
-
-    import torch
-
     from . import api
 
     arr, ns = api.surface_array(surfaces)
     n = offsets.shape[0] - 1
-    dev = offsets.device
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    if capacity is None:
-        api._check(api.lib().srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), None, None, 0,
-                                                  count.data_ptr(), st.cuda_stream))
-        st.synchronize()
-        capacity = int(count.item())
-    if capacity == 0:
-        api._check(api.lib().srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), None, None, 0,
-                                                  count.data_ptr(), st.cuda_stream))
-        return None, None, count
-    ev = torch.zeros((capacity, ROW), dtype=torch.float64, device=dev)
-    meta = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
-    api._check(api.lib().srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), ev.data_ptr(), meta.data_ptr(),
-                                              C.c_int64(capacity), count.data_ptr(), st.cuda_stream))
+
+    def call(ev, meta, dist, cap, count, st):
+        return api.lib().srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), ev, meta, cap, count, st)
+
+    ev, meta, _, count = _events_device(call, offsets, capacity, stream, False)
     return ev, meta, count
 
 

@@ -5,7 +5,6 @@
 #include <cstdio>
 #include <vector>
 
-#define SRT_CROSSINGS_NO_KERNELS
 #define SRT_BINNING_NO_KERNELS
 #include "../../stanford_raytracer_amd/csrc/srt_binning.hpp"
 
