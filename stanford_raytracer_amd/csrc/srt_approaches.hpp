@@ -8,7 +8,7 @@
 // The KERNELS take one lane per packed row (the interval that starts there) and walk the observers, staged through LDS in tiles
 // that every lane reads at the same address (a broadcast).  A pair is first held against the hull of the cubic's Bezier points
 // -- about ten fp64 instructions -- and only a survivor pays for the end signs and the bisection.  A count pass writes one uint32
-// per row, a prefix sum lies between (srt_api.hip), and a fill pass recounts the rows that have events and writes them at the
+// per row, a prefix sum lies between (srt_api_rows.hpp), and a fill pass recounts the rows that have events and writes them at the
 // scanned position: that is what puts the events in (ray, interval, observer) order.
 //
 // Compiles for the device (hipcc) and for the host.

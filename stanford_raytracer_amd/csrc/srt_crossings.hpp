@@ -6,7 +6,7 @@
 // srt_xform.hpp does), so that a host build (tests/native/crossings_host.cpp) and the device give the same bits wherever sqrt
 // does.  The KERNELS are a count pass (one 16-bit surface mask per packed row: bit s = the interval that STARTS at this row holds
 // an event of surface s) and a fill pass that reads only rows whose mask is not zero; a prefix sum of the masks' bit counts
-// lies between them (srt_api.hip), which is what puts the events in (ray, interval, surface) order.
+// lies between them (srt_api_rows.hpp), which is what puts the events in (ray, interval, surface) order.
 //
 // Compiles for the device (hipcc) and for the host.
 #pragma once

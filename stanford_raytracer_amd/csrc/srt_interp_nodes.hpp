@@ -1,7 +1,7 @@
 // srt_interp_nodes.hpp -- modelnum = 3 in its second layout: a node table, the 64 coefficients of a cell built at each lookup.
 //
 // HBM layout:  nodes[k][j][i][species][8]  doubles -- per (node, species) the eight constraint families of
-// build_coeffs_kernel (srt_api.hip) in its order, already scaled by the spacings with that kernel's left-to-right products:
+// build_coeffs_kernel (srt_api_grid.hpp) in its order, already scaled by the spacings with that kernel's left-to-right products:
 //     f, f_x dx, f_y dy, f_z dz, f_xy dx dy, f_xz dx dz, f_yz dy dz, f_xyz dx dy dz
 // One record is 64 B, a node 256 B at four species, corners i and i + 1 are adjacent: a lookup reads four runs of 512 B.
 // nx ny nz nspec 64 bytes: an eighth of the expanded table coef[cell][species][64] (InterpModel, srt_models.hpp).

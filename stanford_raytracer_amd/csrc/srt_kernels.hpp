@@ -46,7 +46,7 @@ struct TraceParams {
   double dt0, dtmax, tmax, maxerr, minalt, del;
   int maxsteps, root, fixedstep, outputper, first_attempt_policy, refill_threshold;
   int slots;
-  int wave_cap; // rays a wave holds at most (64 = every lane; 8 = every trip runs in the Ngo model's tail mode, see srt_api.hip)
+  int wave_cap; // rays a wave holds at most (64 = every lane; 8 = every trip runs in the Ngo model's tail mode, see srt_api_trace.hpp)
 };
 
 struct TraceArgs {

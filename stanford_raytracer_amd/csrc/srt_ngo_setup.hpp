@@ -1,5 +1,5 @@
 // srt_ngo_setup.hpp -- readinput of the Ngo density modules (ngo_dens_model.f95:29-160; ngo_3d_dens_model.f95 has the same) on
-// the host: a parsed card file into the struct the device reads.  Shared by the library (srt_api.hip, which evaluates the
+// the host: a parsed card file into the struct the device reads.  Shared by the library (srt_api_model.hpp, which evaluates the
 // normalisation's one density on the device) and the host build of the density path (tests/native/ngo3d_host.cpp).
 #pragma once
 #include "srt_host.hpp"

@@ -1,7 +1,7 @@
 // Host build of the closest-approach finder -- stanford_raytracer_amd/csrc/srt_approaches.hpp's hull reject, its test function f,
 // its bisection, the per-pair decision and the walk of a row over the observers, the very source the device compiles -- for the
 // CPU tests (tests/test_approaches_host.py).  Compiled as HIP for the host alone, contraction off.  What is restated here because
-// it lives in the kernels and in srt_api.hip: the loop over the rows in place of the two launches, the whole observer array in
+// it lives in the kernels and in srt_api_rows.hpp: the loop over the rows in place of the two launches, the whole observer array in
 // place of the LDS tiles, and the running sum in place of the device scan.
 //
 // As a program: approaches_host < input, where input is "nobs nrays capacity", nobs lines "x y z radius", nrays + 1 offsets, then

@@ -1,7 +1,7 @@
 // Host build of the ray binning -- stanford_raytracer_amd/csrc/srt_binning.hpp's coordinate functions, its edge search, its
 // samples, weights and deposits and the whole routine of a packed row, the very source the device compiles -- for the CPU tests
 // (tests/test_binning_host.py).  Compiled as HIP for the host alone, contraction off.  What is restated here because it lives in
-// the kernel and in srt_api.hip: the loop over the rows in place of the launch, and plain adds in place of the atomics.
+// the kernel and in srt_api_rows.hpp: the loop over the rows in place of the launch, and plain adds in place of the atomics.
 #include <cstdio>
 #include <vector>
 

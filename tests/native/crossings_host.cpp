@@ -1,7 +1,7 @@
 // Host build of the surface-crossing finder -- stanford_raytracer_amd/csrc/srt_crossings.hpp's g, its Hermite curve in the Delta
 // form, its bisection, the mask of a packed row and the events of a row, the very source the device compiles -- for the CPU tests
 // (tests/test_crossings_host.py).  Compiled as HIP for the host alone, contraction off.  What is restated here because it lives
-// in srt_api.hip: the loop over the rows in place of the two launches, and the running sum in place of the device scan.
+// in srt_api_rows.hpp: the loop over the rows in place of the two launches, and the running sum in place of the device scan.
 //
 // As a program: crossings_host < input, where input is "nsurf nrays capacity", nsurf lines "kind p0 p1 p2 p3", nrays + 1 offsets,
 // then the rows (20 numbers each); prints the total, then one line per kept event: ray surface interval direction and the row.

@@ -2,7 +2,7 @@
 // the CPU tests of tests/test_igrf_edges.py: no GPU, no HIP runtime.
 #include "../../stanford_raytracer_amd/csrc/srt_host.cpp"
 
-// what srt_host.cpp's file-format entry points take from srt_api.hip (not called here: only igrf_setup is)
+// what srt_host.cpp's file-format entry points take from srt_api_core.hpp and srt_api_trace.hpp (not called here: only igrf_setup is)
 int srt_set_error(int code, const char *, ...) { return code; }
 extern "C" int srt_rows_per_ray(const srt_params *) { return 0; }
 

@@ -1,7 +1,7 @@
 // Host build of the node-table lookup of modelnum 3 -- stanford_raytracer_amd/csrc/srt_interp_nodes.hpp's gather with its clamp
 // and sticky flags, its 64 unrolled coefficient rows and InterpModel::eval, the very source the device compiles -- for the CPU
 // tests (tests/test_interp_nodes_host.py), checked against the oracle.  Compiled as HIP for the host alone.  What is restated
-// here because it is device-only or lives in srt_api.hip: the finite-difference passes (fd_axis_kernel and their order), the
+// here because it is device-only or lives in srt_api_grid.hpp: the finite-difference passes (fd_axis_kernel and their order), the
 // fill of the node table (build_nodes_kernel) and the cell search (Axis::locate: the count of nodes <= x and the local
 // coordinate), each plainly.
 //
