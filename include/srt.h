@@ -394,6 +394,16 @@ int srt_last_kernel_ms(srt_model *m, float *ms);
 /* the same for the launch `back` launches before the most recent one (0 .. 3): lets a caller that keeps several
  * launches in flight on different streams read their durations afterwards */
 int srt_launch_ms(srt_model *m, int back, float *ms);
+/* The tail stash of that launch (unsegmented launches of the interp model, both layouts): while the queue has fresh rays every
+ * wave banks a few of its own rays when their step count reaches 1/2, 3/4, 7/8, 15/16 of maxsteps, and finishes them in the
+ * lanes that fall idle once the queue is empty.  Rows, nrows, stopcond and counters[0..2] are those of a launch without;
+ * counters[3] (loop trips of all waves) gets smaller.  stats[SRT_STASH_STATS]: rays banked at each of the four marks, rays
+ * resumed, the most records one wave held, loop trips run after a wave saw the queue empty (summed over the waves).  All zero
+ * for a launch that banked nothing: no more rays than lanes, maxsteps < 32, another model, a segmented launch, a refused
+ * allocation, or SRT_TAIL_STASH=0 in the environment (SRT_TAIL_STASH=n: at most n records per wave and mark; read per launch,
+ * like SRT_MAX_BLOCKS=n, which caps the launch's number of waves).  Synchronises the launch's stream. */
+#define SRT_STASH_STATS 7
+int srt_launch_stash_stats(srt_model *m, int back, int64_t *stats);
 
 /* ---- the step after the path: hot-plasma damping along the kept rows ----
  * Replaces the MATLAB post-processor matlab/damping/: test_dampray.m:24-99 (per-row driver, running magnitude),
@@ -458,7 +468,8 @@ typedef struct srt_surface {
  * d_count one int64: it always receives the total; events beyond `capacity` are left out (the first `capacity` events of the
  * defined order are kept).  capacity = 0 with NULL outputs is a count-only call.  The device is found from the buffers, as in
  * srt_pack_rows_device.  The call reads d_offsets[nrays] (8 bytes) behind the work already on `stream`, to size its launches,
- * and checks it against the allocation d_rows points into; from there on it is asynchronous on `stream`. */
+ * and checks it against the allocation d_rows points into, runs its passes on `stream` and returns when they are done (its
+ * scratch is freed then). */
 int srt_crossings_device(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *d_offsets, const double *d_rows,
                          double *d_event_rows, int32_t *d_event_meta, int64_t capacity, int64_t *d_count, void *stream);
 /* The same on host buffers; *event_rows[*nevents][SRT_ROW] and *event_meta[*nevents][4] are malloc'd (srt_free; NULL when there

@@ -85,6 +85,7 @@ MAXSURF = 16  # SRT_MAXSURF
 MAXOBS = 65536  # SRT_MAXOBS
 RUNNING = -1  # SRT_RUNNING: stopcond of a paused ray
 STATE = 17    # SRT_STATE: doubles in a paused ray's record
+STASH_STATS = 7  # SRT_STASH_STATS: counts of srt_launch_stash_stats
 
 
 def library_path():
@@ -161,6 +162,8 @@ def lib():
                                             C.POINTER(C.c_int64), dp, ip]
     L.srt_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.srt_launch_ms.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    if hasattr(L, "srt_launch_stash_stats"):  # (an A/B build of older sources, SRT_LIB_OVERRIDE, has none)
+        L.srt_launch_stash_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
     L.srt_read_rays_file.argtypes = [C.c_char_p, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]
     L.srt_read_rays_file.restype = C.c_int64
     L.srt_write_ray_file.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.POINTER(Params), C.c_int, dp, dp,
@@ -550,6 +553,14 @@ class Model:
         ms = C.c_float()
         _check(lib().srt_launch_ms(self.h, back, C.byref(ms)))
         return float(ms.value)
+
+    def stash_stats(self, back=0):
+        """The tail stash of a past trace launch (include/srt.h, srt_launch_stash_stats): a dict of banked[4] (rays banked at
+        1/2, 3/4, 7/8, 15/16 of maxsteps), resumed, max_fill (most records one wave held) and tail_trips (loop trips after
+        a wave saw the queue empty).  All zero for a launch that banked nothing."""
+        s = (C.c_int64 * STASH_STATS)()
+        _check(lib().srt_launch_stash_stats(self.h, back, s))
+        return {"banked": [int(v) for v in s[0:4]], "resumed": int(s[4]), "max_fill": int(s[5]), "tail_trips": int(s[6])}
 
     def last_kernel_ms(self):
         ms = C.c_float()

@@ -28,6 +28,7 @@
 #include "srt_interp_nodes.hpp"
 #include "srt_simple3d.hpp"
 #include "srt_at64thch.hpp"
+#include "srt_tail_stash.hpp"
 
 using namespace srt;
 
@@ -224,6 +225,7 @@ struct srt_model {
     DevBytes sorttmp;
     Scratch stage; // staging records of coop_stencil, REC_CAP * REC doubles per block
     Scratch cand;  // the lanes' candidate blocks, BLOCK_DOUBLES per block
+    Scratch stash; // interp model: the waves' tail stash (srt_tail_stash.hpp), sum of quotas * STASH_REC doubles per block
     // frees the scratch and forgets refused sizes; the caller has waited for `done` where a launch may still read it
     void release() {
       for (int k = 0; k < 2; ++k) {
@@ -233,7 +235,8 @@ struct srt_model {
       sorttmp.release();
       stage.buf.release();
       cand.buf.release();
-      stage.blocks = stage.failed = cand.blocks = cand.failed = 0;
+      stash.buf.release();
+      stage.blocks = stage.failed = cand.blocks = cand.failed = stash.blocks = stash.failed = 0;
     }
   };
   static constexpr int NSLOT = 4;
@@ -243,6 +246,8 @@ struct srt_model {
   struct LaunchTimes {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool used = false;
+    DevBuf<unsigned long long> stats; // [STASH_STATS], written by the launch's waves (srt_launch_stash_stats)
+    bool stashed = false;             // that launch banked rays: `stats` is its own
   };
   static constexpr int NHIST = 4;
   LaunchTimes hist[NHIST];

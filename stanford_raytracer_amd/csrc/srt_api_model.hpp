@@ -52,6 +52,7 @@ static int model_finish(srt_model *m) {
   for (auto &h : m->hist) {
     HIP_OK(hipEventCreate(&h.ev0));
     HIP_OK(hipEventCreate(&h.ev1));
+    HIP_OK(h.stats.alloc(STASH_STATS));
   }
   return SRT_OK;
 }
@@ -380,7 +381,7 @@ extern "C" int srt_model_create_scattered_file_root(const char *ptsfile, int yea
 static void scratch_refused(srt_model *m, const char *what, size_t bytes) {
   if (m->warned_scratch) return;
   m->warned_scratch = true;
-  fprintf(stderr, "libsrt_hip: hipMalloc of %.2f GB for the scattered model's %s was refused; tracing without them (slower). "
+  fprintf(stderr, "libsrt_hip: hipMalloc of %.2f GB for %s was refused; tracing without them (slower). "
                   "srt_model_trim() on this or other models releases launch scratch.\n", (double)bytes / 1e9, what);
 }
 // SRT_SCATTERED_STAGING=0 in the environment: no staging buffer, i.e. the own-list path for every stencil (tests hold

@@ -243,35 +243,34 @@ extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int6
   if (capacity > 0 && (!within_allocation(d_event_rows, (size_t)capacity * SRT_ROW * sizeof(double)) ||
                        !within_allocation(d_event_meta, (size_t)capacity * 4 * sizeof(int32_t))))
     return srt_set_error(SRT_EINVAL, "srt_crossings_device: an output has no room for capacity = %lld events", (long long)capacity);
-  // scratch on the stream: mask[total] (2 B a row), evoff[total + 1] (8 B a row), the scan's own
+  // Scratch: mask[total] (2 B a row), evoff[total + 1] (8 B a row), the scan's own.  Plain allocations and a wait for the stream
+  // before they are freed, as srt_approaches_device below and for its reason: this call comes in pairs (count, then fill), and
+  // with hipMallocAsync / hipFreeAsync the second call of a process found recycled blocks -- a tool-mode run of the executable
+  // once wrote its events' metadata as zeros, with the right count.
   static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-  uint16_t *mask = nullptr;
-  long long *evoff = nullptr;
-  void *tmp = nullptr;
-  HIP_OK(hipMallocAsync((void **)&evoff, ((size_t)total + 1) * sizeof(long long), st));
-  hipError_t e = hipMallocAsync((void **)&mask, (size_t)total * sizeof(uint16_t), st);
+  DevBuf<uint16_t> mask;
+  DevBuf<long long> evoff;
+  DevBytes tmp;
+  HIP_OK(evoff.alloc((size_t)total + 1));
+  HIP_OK(mask.alloc((size_t)total));
   size_t need = 0;
   auto counts = hipcub::TransformInputIterator<long long, cx::MaskCount, hipcub::CountingInputIterator<long long>>(
-      hipcub::CountingInputIterator<long long>(0), cx::MaskCount{mask, total});
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, evoff, (int)(total + 1), st);
-  if (e == hipSuccess) e = hipMallocAsync(&tmp, need ? need : 16, st);
-  if (e == hipSuccess) {
-    const unsigned blocks = grid_blocks(total, 256);
-    hipLaunchKernelGGL(cx::crossings_count_kernel, dim3(blocks), dim3(256), 0, st, S, (long long)nrays,
-                       (const long long *)d_offsets, total, d_rows, mask);
-    e = hipcub::DeviceScan::ExclusiveSum(tmp, need, counts, evoff, (int)(total + 1), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_count, evoff + total, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && capacity > 0)
-      hipLaunchKernelGGL(cx::crossings_fill_kernel, dim3(blocks), dim3(256), 0, st, S, (long long)nrays,
-                         (const long long *)d_offsets, total, d_rows, (const uint16_t *)mask, (const long long *)evoff,
-                         (long long)capacity, d_event_rows, d_event_meta);
-    if (e == hipSuccess) e = hipGetLastError();
-  }
-  // (also on the error path)
-  if (tmp) (void)hipFreeAsync(tmp, st);
-  if (mask) (void)hipFreeAsync(mask, st);
-  (void)hipFreeAsync(evoff, st);
+      hipcub::CountingInputIterator<long long>(0), cx::MaskCount{mask.p, total});
+  HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, evoff.p, (int)(total + 1), st));
+  HIP_OK(tmp.alloc(need ? need : 16));
+  const unsigned blocks = grid_blocks(total, 256);
+  hipLaunchKernelGGL(cx::crossings_count_kernel, dim3(blocks), dim3(256), 0, st, S, (long long)nrays, (const long long *)d_offsets,
+                     total, d_rows, mask.p);
+  hipError_t e = hipcub::DeviceScan::ExclusiveSum((void *)tmp.p, need, counts, evoff.p, (int)(total + 1), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_count, evoff.p + total, sizeof(int64_t), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess && capacity > 0)
+    hipLaunchKernelGGL(cx::crossings_fill_kernel, dim3(blocks), dim3(256), 0, st, S, (long long)nrays,
+                       (const long long *)d_offsets, total, d_rows, (const uint16_t *)mask.p, (const long long *)evoff.p,
+                       (long long)capacity, d_event_rows, d_event_meta);
+  if (e == hipSuccess) e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(st); // (also on the error path: the scratch goes away when this returns)
   HIP_OK(e);
+  HIP_OK(es);
   return SRT_OK;
 }
 
@@ -377,7 +376,7 @@ extern "C" int srt_approaches_device(int nobs, const srt_observer *observers, in
                        !within_allocation(d_event_dist, (size_t)capacity * sizeof(double))))
     return srt_set_error(SRT_EINVAL, "srt_approaches_device: an output has no room for capacity = %lld events", (long long)capacity);
   // Scratch: the observers, count[total] (4 B a row), evoff[total + 1] (8 B a row), the scan's own.  It is NOT taken from the
-  // stream-ordered allocator as the crossings take theirs: with hipMallocAsync / hipFreeAsync here, the second call of a process
+  // stream-ordered allocator: with hipMallocAsync / hipFreeAsync here, the second call of a process
   // found recycled blocks and counted no events in 4 of 12 fresh processes on an MI355X (the first call never failed).  Plain
   // allocations, a synchronous copy of the observers, and a wait for the stream before they are freed.
   static_assert(sizeof(long long) == sizeof(int64_t), "int64");

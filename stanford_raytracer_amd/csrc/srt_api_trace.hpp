@@ -79,6 +79,7 @@ struct SegLaunch {
   double *state;
 };
 static_assert(SRT_STATE == TRACE_STATE, "srt.h and srt_kernels.hpp disagree on a paused ray's record");
+static_assert(SRT_STASH_STATS == STASH_STATS, "srt.h and srt_tail_stash.hpp disagree on the stash statistics");
 
 // the one launch path of the trace kernels: arguments checked by the two entry points below
 static int trace_launch(srt_model *m, const srt_params *p, int64_t nrays, const double *d_pos0, const double *d_dir0,
@@ -136,6 +137,12 @@ static int trace_launch(srt_model *m, const srt_params *p, int64_t nrays, const 
   a.p.wave_cap = cap;
   long long want = (nwork + cap - 1) / cap;
   if (grid > want) grid = want;
+  // SRT_MAX_BLOCKS=n caps the persistent grid (an experiment and test switch like the two above: a few hundred rays then queue
+  // up behind a handful of waves)
+  if (const char *e = getenv("SRT_MAX_BLOCKS")) {
+    const long long v = atoll(e);
+    if (v >= 1 && grid > v) grid = v;
+  }
   if (grid < 1) grid = 1;
   // scratch slot: one whose last launch is over (preferring one that holds buffers already), else a fresh one, else -- all
   // busy -- the next in turn, which this stream then waits for
@@ -191,11 +198,37 @@ static int trace_launch(srt_model *m, const srt_params *p, int64_t nrays, const 
   // it scans the cells for every stencil -- only slower
   a.scratch = a.scratch2 = nullptr;
   if (m->kind == KIND_SCATTERED && staging_enabled() &&
-      (rc = slot_scratch(m, sl, sl.stage, grid, (size_t)ScatteredModel::REC_CAP * ScatteredModel::REC, "staging records", &a.scratch)))
+      (rc = slot_scratch(m, sl, sl.stage, grid, (size_t)ScatteredModel::REC_CAP * ScatteredModel::REC, "the scattered model's staging records", &a.scratch)))
     return rc;
   if (m->kind == KIND_SCATTERED && a.scratch != nullptr && blocks_enabled() &&
-      (rc = slot_scratch(m, sl, sl.cand, grid, ScatteredModel::BLOCK_DOUBLES, "candidate blocks", &a.scratch2)))
+      (rc = slot_scratch(m, sl, sl.cand, grid, ScatteredModel::BLOCK_DOUBLES, "the scattered model's candidate blocks", &a.scratch2)))
     return rc;
+  // Tail stash of the unsegmented interp kernels (srt_tail_stash.hpp): a block of the slot's scratch per wave; a refused
+  // allocation means a launch without banking.  SRT_TAIL_STASH=n caps the quota of every mark at n records; 0 = no banking.
+  TraceStashArgs sa;
+  sa.stash = nullptr;
+  sa.stats = nullptr;
+  lt.stashed = false;
+  {
+    int quota_cap = -1;
+    if (const char *e = getenv("SRT_TAIL_STASH")) quota_cap = atoi(e) < 0 ? 0 : atoi(e);
+    const bool traits = !sg && (m->kind == KIND_INTERP || m->kind == KIND_INTERP_NODES);
+    sa.sp = stash_policy(p->maxsteps, traits ? nwork : 0, grid * cap, quota_cap);
+    const int per_wave = stash_total_quota(sa.sp);
+    if (per_wave > 0) {
+      const size_t need = (size_t)grid * (size_t)per_wave * STASH_REC;
+      if (sl.stash.buf.cap < need) sl.stash.blocks = 0; // (the block per wave grew with the quota: what is held counts for nothing)
+      if ((rc = slot_scratch(m, sl, sl.stash, grid, (size_t)per_wave * STASH_REC, "the interp model's tail stash", &sa.stash))) return rc;
+      if (sa.stash != nullptr && sl.stash.buf.cap >= need) {
+        sa.stats = lt.stats.p;
+        lt.stashed = true;
+        HIP_OK(hipMemsetAsync(sa.stats, 0, STASH_STATS * sizeof(unsigned long long), st));
+      } else {
+        sa.stash = nullptr;
+        sa.sp = stash_policy(p->maxsteps, 0, 0, 0);
+      }
+    }
+  }
   const bool fixed = p->fixedstep != 0;
   const int fopt = m->cm.fld.use_tsy != 0 ? 2 : (m->cm.fld.use_igrf != 0 ? 1 : 0);
   // one instantiation per (model, integrator, field option): the dipole kernels carry none of the IGRF code, the
@@ -203,11 +236,15 @@ static int trace_launch(srt_model *m, const srt_params *p, int64_t nrays, const 
   rc = with_model(m, [&](auto tag) -> int {
     using T = decltype(tag);
     using M = typename T::Model;
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVE), 0, st, m->on_device<M>(), m->d_common.p, a);
-    };
     auto pick = [&](auto seg) { // (its segmented twin beside every kernel)
       constexpr bool SEG = decltype(seg)::value;
+      auto launch = [&](auto kernel) {
+        if constexpr (!SEG && tail_stash<M>()) {
+          static_cast<TraceArgs &>(sa) = a; // (the TraceArgs part of `a`)
+          hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVE), 0, st, m->on_device<M>(), m->d_common.p, sa);
+        } else
+          hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVE), 0, st, m->on_device<M>(), m->d_common.p, a);
+      };
       if (fixed) {
         if (fopt == 2) launch(trace_kernel<M, true, T::lds, 2, SEG>);
         else if (fopt == 1) launch(trace_kernel<M, true, T::lds, 1, SEG>);
@@ -366,6 +403,21 @@ extern "C" int srt_launch_ms(srt_model *m, int back, float *ms) {
 }
 
 extern "C" int srt_last_kernel_ms(srt_model *m, float *ms) { return srt_launch_ms(m, 0, ms); }
+
+extern "C" int srt_launch_stash_stats(srt_model *m, int back, int64_t *stats) {
+  if (!m || !stats) return srt_set_error(SRT_EINVAL, "null argument");
+  if (back < 0 || back >= srt_model::NHIST || m->last_hist < 0) return srt_set_error(SRT_EINVAL, "no such launch");
+  srt_model::LaunchTimes &lt = m->hist[(m->last_hist - back + srt_model::NHIST) % srt_model::NHIST];
+  if (!lt.used) return srt_set_error(SRT_EINVAL, "no such launch");
+  for (int i = 0; i < SRT_STASH_STATS; ++i) stats[i] = 0;
+  if (!lt.stashed) return SRT_OK; // a launch without banking
+  SRT_MODEL_SCOPE;
+  int rc = ensure_model(m);
+  if (rc) return rc;
+  HIP_OK(hipEventSynchronize(lt.ev1));
+  HIP_OK(hipMemcpy(stats, lt.stats.p, SRT_STASH_STATS * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return SRT_OK;
+}
 
 // AoS [n][3] -> SoA [3][n]
 __global__ void aos_to_soa3(const double *in, double *out, long long n) {

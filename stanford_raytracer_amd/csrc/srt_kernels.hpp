@@ -8,6 +8,8 @@
 #pragma once
 #include "srt_models.hpp"
 #include "srt_ngo3d.hpp"
+#include "srt_interp_nodes.hpp"
+#include "srt_tail_stash.hpp"
 
 namespace srt {
 
@@ -76,6 +78,22 @@ __device__ __forceinline__ int segment_of(const TraceSegArgs &a) { return a.segm
 // A paused ray's record: x[6], r1[6] (the carried first stage), vg[3], t, dt (srt.h: SRT_STATE).  nstep travels in nrows;
 // lastrefinedown is 0 and first_attempt is nstep == 1 wherever a ray can pause.
 constexpr int TRACE_STATE = 17;
+static_assert(STASH_REC == TRACE_STATE + 1, "a stash record is a paused ray's record and its ray id");
+
+// Tail stash (srt_tail_stash.hpp): the unsegmented kernels of these models bank a few of their own rays per wave at fixed step
+// counts while the queue has fresh rays, and finish them in the lanes that fall idle once it is empty.  A resumed ray's rows
+// are bit-equal (it is the SEG pause and resume inside one launch).  Not the scattered model (a resumed ray's candidate block
+// reorders its sums), not Ngo and its kin (their launches end in tail mode, spread_rhs).
+template <class M>
+constexpr bool tail_stash() {
+  return std::is_same<M, InterpModel>::value || std::is_same<M, InterpNodesModel>::value;
+}
+// what those kernels take: TraceArgs, and behind it (the other kernels' argument block is the one it was)
+struct TraceStashArgs : TraceArgs {
+  double *stash;             // [grid][sum of quotas][STASH_REC], or nullptr: no banking
+  unsigned long long *stats; // [STASH_STATS]: banked per mark, resumed, largest fill of a wave, trips after the queue was seen empty
+  StashPolicy sp;
+};
 
 // Stencil of raytracer_evalrhs: centre + the six points x +- d e_c of dispersion_relation_dFdx
 // (raytracer.f95:239-262).  p[0] centre, p[1+2c] = x + d_c e_c, p[2+2c] = x - d_c e_c.
@@ -367,7 +385,8 @@ __device__ __forceinline__ void store_row(double *row, double t, const double x[
 // segment they are restored from their records and go straight to `active` (no ride-along trip, no row 0), so a ray's
 // arithmetic is that of the unsegmented launch.  counters[1] counts the steps accepted in THIS launch.
 template <class M, bool FIXED, bool USE_LDS, int FOPT = 0, bool SEG = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M>::WAVES_PER_EU))) void trace_kernel(const M *__restrict__ mp, const Common *__restrict__ cp, typename std::conditional<SEG, TraceSegArgs, TraceArgs>::type a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M>::WAVES_PER_EU))) void trace_kernel(const M *__restrict__ mp, const Common *__restrict__ cp, typename std::conditional<SEG, TraceSegArgs, typename std::conditional<tail_stash<M>(), TraceStashArgs, TraceArgs>::type>::type a) {
+  constexpr bool STASH = !SEG && tail_stash<M>();
   const M &m = *mp;
   constexpr bool IGRF = FOPT != 0;
   typedef typename std::conditional<FOPT == 0, CommonDipole, typename std::conditional<FOPT == 1, CommonIgrfOnly, CommonIgrf>::type>::type CM;
@@ -395,6 +414,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
   const int threshold = P.refill_threshold > 0 ? P.refill_threshold : 1;
   long long nwork = a.nrays; // rays in the queue
   if constexpr (SEG) nwork = a.nqueue;
+  // tail stash, all wave-uniform: records held per level, rays banked per level, rays resumed, trips since the queue was seen empty
+  int st_fill[STASH_LEVELS] = {0, 0, 0, 0}, st_banked[STASH_LEVELS] = {0, 0, 0, 0}, st_resumed = 0;
+  unsigned long long st_tail_trips = 0;
 #ifdef SRT_PHASE_TIMING
   const unsigned long long srt_wave_t0 = __builtin_readcyclecounter();
 #endif
@@ -437,6 +459,46 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
         a.stopcond[ray] = -1; // SRT_RUNNING
         acc_steps += (unsigned long long)(nstep - 1);
         active = false;
+      }
+    }
+    if constexpr (STASH) {
+      // bank: while the queue has fresh rays, a ray that stands on a mark right behind an accepted step (behind a rejected attempt
+      // nstep is unchanged but the state is not the one SEG stores) goes into this wave's stash, and its lane claims a fresh
+      // ray below, in this trip.  Written and read by this wave alone.
+      if (a.stash != nullptr && !queue_empty) { // wave-uniform
+        const int lvl = (active && lastrefinedown == 0) ? stash_bank_level(a.sp, nstep) : -1;
+        if (__any(lvl >= 0)) {
+          int first = 0; // the level's first record in the wave's block
+#pragma unroll
+          for (int k = 0; k < STASH_LEVELS; ++k) {
+            const unsigned long long want = __ballot(lvl == k);
+            const int left = a.sp.quota[k] - st_fill[k];
+            if (want != 0ull && left > 0) {
+              const int rank = __popcll(want & ((1ull << lane) - 1ull));
+              if (lvl == k && rank < left) {
+                double *s = a.stash + ((size_t)blockIdx.x * (size_t)stash_total_quota(a.sp) + (size_t)(first + st_fill[k] + rank)) * STASH_REC;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                  s[c] = x[c];
+                  s[6 + c] = r1[c];
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s[12 + c] = vg[c];
+                s[15] = t;
+                s[16] = dt;
+                s[17] = __longlong_as_double(ray);
+                a.nrows[ray] = nstep;
+                active = false;
+              }
+              const int n = __popcll(want);
+              const int took = n < left ? n : left;
+              st_fill[k] += took;
+              st_banked[k] += took;
+            }
+            first += a.sp.quota[k];
+          }
+          __threadfence_block(); // block == one wave: the records are written before any lane of it reads them back
+        }
       }
     }
     // ---- B. refill free lanes from the queue (ballot compaction)
@@ -491,13 +553,69 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
       }
       if ((long long)base + take >= nwork) queue_empty = true;
     }
+    if constexpr (STASH) {
+      // resume: the queue is empty, so free lanes take this wave's banked rays (the same compaction, the same wave_cap).  The
+      // level is chosen for the wave (stash_pick), level after level until the lanes or the stash run out.
+      if (queue_empty && st_fill[0] + st_fill[1] + st_fill[2] + st_fill[3] > 0) { // wave-uniform
+        const bool idle = !active && !needinit;
+        const unsigned long long idlemask = __ballot(idle);
+        const int nidle = __popcll(idlemask);
+        const int room2 = P.wave_cap - (WAVE - nidle);
+        const int take2 = nidle < room2 ? nidle : (room2 > 0 ? room2 : 0);
+        if (take2 > 0) {
+          const int rank = __popcll(idlemask & ((1ull << lane) - 1ull));
+          int mine = -1, given = 0; // this lane's record in the wave's block; lanes served so far
+#pragma unroll 1
+          for (int it = 0; it < STASH_LEVELS && given < take2; ++it) {
+            const int k = stash_pick(a.sp, st_fill, P.maxsteps, (long long)st_tail_trips);
+            if (k < 0) break;
+            int first = 0, have = 0;
+#pragma unroll
+            for (int q = 0; q < STASH_LEVELS; ++q) {
+              first += q < k ? a.sp.quota[q] : 0;
+              have = q == k ? st_fill[q] : have;
+            }
+            const int n = have < take2 - given ? have : take2 - given;
+            if (idle && rank >= given && rank < given + n) mine = first + have - 1 - (rank - given);
+#pragma unroll
+            for (int q = 0; q < STASH_LEVELS; ++q) st_fill[q] -= q == k ? n : 0;
+            given += n;
+          }
+          st_resumed += given;
+          if (mine >= 0) {
+            new_ray_hook(m, lds, true);
+            const double *s = a.stash + ((size_t)blockIdx.x * (size_t)stash_total_quota(a.sp) + (size_t)mine) * STASH_REC;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+              x[c] = s[c];
+              r1[c] = s[6 + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) vg[c] = s[12 + c];
+            t = s[15];
+            dt = s[16];
+            ray = __double_as_longlong(s[17]);
+            nstep = a.nrows[ray];
+            lastrefinedown = 0;
+            first_attempt = nstep == 1;
+            w = a.w0[ray];
+            active = true;
+          }
+        }
+      }
+    }
     // ---- C. (newly claimed rays have no step of their own this trip: they ride along with the running ones and
     // their launch point takes the place of the step's end point in E/F/G, see there; :661-742.  Every ray is
     // initialised by that one code path, so its arithmetic does not depend on when it was claimed.)
     // ---- D. exit when nothing is left (every wave reaches this)
     if (!__any(active || needinit)) {
-      if (queue_empty) break;
+      // (tail stash: with the queue empty and every lane idle the resume above has taken whatever the stash held -- wave_cap is at
+      // least 1 -- so the stash is empty here; tested all the same, and every condition is the wave's own)
+      if (queue_empty && (!STASH || st_fill[0] + st_fill[1] + st_fill[2] + st_fill[3] == 0)) break;
       continue;
+    }
+    if constexpr (STASH) {
+      if (queue_empty) ++st_tail_trips;
     }
 
     // ---- E. one attempt for every lane (:770-817).  Stage 1 = r1 (carried); stages 2.. are evaluated here.
@@ -755,6 +873,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WaveBudget<M
     atomicAdd(a.counters + 1, acc_steps);
     atomicAdd(a.counters + 2, acc_attempts);
     atomicAdd(a.counters + 3, wave_trips);
+  }
+  if constexpr (STASH) {
+    if (lane == 0 && a.stats != nullptr && st_tail_trips > 0) {
+      int all = 0;
+#pragma unroll
+      for (int k = 0; k < STASH_LEVELS; ++k) {
+        if (st_banked[k] > 0) atomicAdd(a.stats + k, (unsigned long long)st_banked[k]);
+        all += st_banked[k];
+      }
+      if (all > 0) {
+        atomicAdd(a.stats + STASH_LEVELS, (unsigned long long)st_resumed);
+        atomicMax(a.stats + STASH_LEVELS + 1, (unsigned long long)all); // (a wave's fill only grows until it sees the queue empty)
+      }
+      atomicAdd(a.stats + STASH_LEVELS + 2, st_tail_trips);
+    }
   }
 }
 
