@@ -605,6 +605,59 @@ int srt_approaches(int nobs, const srt_observer *observers, int64_t nrays, const
 int srt_approaches_file_write(const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
                               const double *event_dist, const double *event_rows);
 
+/* ---- ray tubes: the cross-section a ray and two neighbour rays span, and with it geometric spreading ----
+ * No piece of the reference does this (matlab/ only plots).  In geometric optics the power a ray carries divides by the
+ * cross-section of the tube that the ray and its neighbours span; the power maps above weight by the damping alone.
+ * INPUT: the PACKED layout of the crossings, offsets[nrays + 1] (offsets[0] = 0) and rows[offsets[nrays]][SRT_ROW], and
+ * neighbours[nrays][2], int64, in HOST memory (as surfaces and observers are): for ray a the indices b, c of the two rays that
+ * span its tube; -1, -1 means "ray a has no tube".
+ * POSITION OF A NEIGHBOUR AT TIME t (t = column 0 of a centre row).  The neighbour ray has n kept rows r_0 .. r_{n-1}.
+ *   1. Search: lo = 0, hi = n; while lo < hi: mid = lo + (hi - lo) / 2; if t_mid <= t then lo = mid + 1, else hi = mid;
+ *      i = lo - 1.  A NaN t_mid compares false.  Nothing else is assumed about the order of the times.
+ *   2. i < 0: there is no row at this time.
+ *   3. t_i == t: q = pos_i as it stands, provided its three components are finite; if they are not, the result is unusable.  No
+ *      curve and no interval are needed: a fixed-step trace, whose rays share their time stamps, never interpolates, and a
+ *      neighbour of one row answers at its own time.
+ *   4. Otherwise, i == n - 1: there is no row at this time (the neighbour stopped earlier).
+ *   5. Otherwise the interval (i, i + 1) must be usable by the crossings' rule (t, pos, vgrel finite at both ends,
+ *      t_{i+1} != t_i) and t_{i+1} > t; if not, the result is unusable.
+ *   6. sigma = (t - t_i) / (t_{i+1} - t_i), and q = p(sigma) on the crossings' cubic Hermite curve of the interval, evaluated
+ *      as p0 + sigma (m0 + sigma (c2 + sigma c3)).
+ * SECTION: with p the centre row's position, d_b = q_b - p, d_c = q_c - p:
+ *   Sigma = 1/2 (d_b x d_c), the area vector of the equal-group-time triangle, in m^2;
+ *   A_perp = (Sigma . vg) / |vg|, vg the centre row's vgrel (columns 7 .. 9), |vg| = sqrt(vx^2 + vy^2 + vz^2).
+ * Every product and sum is as written, unfused, summed x, y, z in that order; only + - * / and sqrt are used.  A_perp is
+ * signed: a change of sign along a ray means the tube has folded (a caustic).  The flux of a tube that carries power P is
+ * P magnitude^2 / |A_perp|, to first order in the tube's width.
+ * OUTPUT per packed row: section[total][4] = (Sigma x, Sigma y, Sigma z, A_perp) and flag[total], int32.  The steps run in
+ * this order and the first flag that is met is set -- neighbour b is examined before c:
+ *   0  ok                                                                               all four values
+ *   1  the ray has no tube                                                              four NaN
+ *   2  the centre row's t or pos is not finite                                          four NaN
+ *   3  a neighbour has no row at this time (no rows at all, before its first, after its last)   four NaN
+ *   4  a neighbour's row or interval is unusable                                        four NaN
+ *   5  vg has a component that is not finite, or |vg| as computed is 0 or not finite    Sigma written, A_perp NaN
+ * Rows of different packed sets (the segments of a segmented trace, taken one by one) do not see each other: a neighbour row
+ * that lies in another set is "no row at this time".  What the kept rows do not show is not seen: between its rows the
+ * neighbour moves on the Hermite cubic.
+ * SRT_EINVAL, by name, before a device is looked at: neighbours NULL, a pair with exactly one -1, an index outside
+ * [0, nrays), b == c, b == a or c == a, both outputs NULL; host offsets that decrease or do not start at 0. */
+/* On buffers resident in device memory (`neighbours` is host memory).  d_section[offsets[nrays]][4], d_flag[offsets[nrays]];
+ * either may be NULL, not both.  The device is found from the buffers, as in srt_pack_rows_device.  The call reads
+ * d_offsets[nrays] (8 bytes) behind the work already on `stream`, to size its launch, and checks it against the allocations
+ * d_rows and the outputs point into (at most 2^31 - 2 rows); it copies the neighbours up, runs its pass on `stream` and
+ * returns when it is done (the neighbours' copy is freed then). */
+int srt_tubes_device(int64_t nrays, const int64_t *neighbours, const int64_t *d_offsets, const double *d_rows, double *d_section,
+                     int32_t *d_flag, void *stream);
+/* The same on host buffers; section[offsets[nrays]][4] and flag[offsets[nrays]] are the caller's (either may be NULL, not
+ * both). */
+int srt_tubes(int64_t nrays, const int64_t *neighbours, const int64_t *offsets, const double *rows, double *section, int32_t *flag);
+/* One record per packed row whose flag is not 1, (3 i10, 5 es24.15e3): raynum[ray] (the caller's number of the row's ray), the
+ * row's index among its ray's kept rows + 1, the flag, t, Sigma x, Sigma y, Sigma z, A_perp, formatted as the .ray writer
+ * formats (NaN as that writer writes it).  A ray number outside 0 .. 9999999999 is refused.  Pure host code, needs no GPU. */
+int srt_tubes_file_write(const char *path, int64_t nrays, const int64_t *raynum, const int64_t *offsets, const double *rows,
+                         const double *section, const int32_t *flag);
+
 /* ---- file formats of the boundary ---- */
 /* ray input file: 7 list-directed reals per line (raytracer_driver.f95:1146); returns count, fills
  * malloc'd arrays the caller frees with srt_free */

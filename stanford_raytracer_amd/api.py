@@ -202,6 +202,9 @@ def lib():
     L.srt_approaches_device.argtypes = [C.c_int, obp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, vp, vp]
     L.srt_approaches.argtypes = [C.c_int, obp, C.c_int64, i64p, dp, i64p, C.POINTER(dp), C.POINTER(ip), C.POINTER(dp)]
     L.srt_approaches_file_write.argtypes = [C.c_char_p, C.c_int64, i64p, ip, dp, dp]
+    L.srt_tubes_device.argtypes = [C.c_int64, i64p, vp, vp, vp, vp, vp]
+    L.srt_tubes.argtypes = [C.c_int64, i64p, i64p, dp, dp, ip]
+    L.srt_tubes_file_write.argtypes = [C.c_char_p, C.c_int64, i64p, i64p, dp, dp, ip]
     bpp = C.POINTER(BinParams)
     L.srt_bin_rays_device.argtypes = [bpp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
     L.srt_bin_rays.argtypes = [bpp, C.c_int64, i64p, dp, dp, dp, C.POINTER(i64p), C.POINTER(i64p), i64p]
@@ -848,6 +851,100 @@ def write_approaches_file(path, raynum, meta, dist, event_rows):
         raise ValueError("raynum, meta, dist and event_rows name %d, %d, %d and %d events" % (len(raynum), len(meta), len(dist), len(event_rows)))
     _check(lib().srt_approaches_file_write(os.fsencode(path), len(meta), raynum.ctypes.data_as(C.POINTER(C.c_int64)),
                                            meta.ctypes.data_as(ip), _dp(dist), _dp(event_rows)))
+
+
+# ---- ray tubes: the cross-section a ray and two neighbours span (include/srt.h) -------
+def neighbour_table(neighbours, nrays):
+    """neighbours as the C ABI takes them -> int64[nrays, 2], contiguous (-1, -1: no tube)."""
+    nb = np.ascontiguousarray(neighbours, dtype=np.int64).reshape(-1, 2)
+    if len(nb) != nrays:
+        raise ValueError("neighbours holds %d pairs for %d rays" % (len(nb), nrays))
+    return nb if len(nb) else np.full((1, 2), -1, dtype=np.int64)
+
+
+def tubes(offsets, rows, neighbours):
+    """The section of every ray's tube at each of its kept rows: neighbours[n, 2] names the two rays that span ray a's tube
+    (-1, -1: none), each is taken at the row's time on the cubic Hermite curve through its own kept rows -> (section[total, 4] =
+    the area vector of the triangle (m^2) and its component along the row's group velocity, A_perp, signed; flag[total] int32:
+    0 ok, 1 no tube, 2 bad centre row, 3 a neighbour has no row at this time, 4 a neighbour's row or interval is unusable,
+    5 no group velocity).  The flux of a tube of power P is P magnitude^2 / |A_perp|."""
+    offsets, rows = _packed(offsets, rows)
+    n, total = offsets.size - 1, int(offsets[-1])
+    nb = neighbour_table(neighbours, n)
+    section = np.full((max(total, 0), 4), np.nan)
+    flag = np.ones(max(total, 0), dtype=np.int32)
+    _check(lib().srt_tubes(n, nb.ctypes.data_as(C.POINTER(C.c_int64)), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(rows),
+                           _dp(section), flag.ctypes.data_as(ip)))
+    return section, flag
+
+
+def tubes_padded(rows, nrows, outputper, neighbours):
+    """tubes() of rows[n, slots, 20], nrows[n] as Model.trace returns them: packs first."""
+    offsets, packed = pack_rows(rows, nrows, outputper)
+    return tubes(offsets, packed, neighbours)
+
+
+def write_tubes_file(path, raynum, offsets, rows, section, flag):
+    """One record per packed row whose flag is not 1, (3 i10, 5 es24.15e3): raynum[ray], the row's index in its ray + 1, the flag,
+    t, the area vector, A_perp."""
+    offsets, rows = _packed(offsets, rows)
+    total = int(offsets[-1])
+    raynum = np.ascontiguousarray(raynum, dtype=np.int64).reshape(-1)
+    section = _f64(section).reshape(-1, 4)
+    flag = np.ascontiguousarray(flag, dtype=np.int32).reshape(-1)
+    if len(raynum) != offsets.size - 1 or len(section) < total or len(flag) < total:
+        raise ValueError("raynum, section and flag name %d rays, %d and %d rows: the packed set has %d rays, %d rows"
+                         % (len(raynum), len(section), len(flag), offsets.size - 1, total))
+    _check(lib().srt_tubes_file_write(os.fsencode(path), offsets.size - 1, raynum.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      offsets.ctypes.data_as(C.POINTER(C.c_int64)), _dp(rows), _dp(section), flag.ctypes.data_as(ip)))
+
+
+def tube_frame(direction):
+    """The two vectors across a ray that tube_fan offsets along, for direction[n, 3] -> (u[n, 3], v[n, 3]).  With d = direction /
+    |direction| and e the coordinate axis along which |d| is smallest (the first such axis of x, y, z): u = (d x e) / |d x e|,
+    v = (d x u) / |d x u|.  u, v and d are unit and perpendicular to one another, and u x v = d."""
+    d = _f64(direction).reshape(-1, 3)
+    d = d / np.sqrt((d * d).sum(axis=1))[:, None]
+    e = np.zeros_like(d)
+    e[np.arange(len(d)), np.argmin(np.abs(d), axis=1)] = 1.0
+    u = np.cross(d, e)
+    u = u / np.sqrt((u * u).sum(axis=1))[:, None]
+    v = np.cross(d, u)
+    v = v / np.sqrt((v * v).sum(axis=1))[:, None]
+    return u, v
+
+
+def tube_fan(pos0, dir0, w0, delta_pos=None, delta_angle=None):
+    """A launch set whose rays carry their own tubes: each ray of (pos0[n, 3], dir0[n, 3], w0[n]) is followed by two companions
+    -> (pos[3n, 3], dir[3n, 3], w[3n], neighbours[3n, 2]); ray k of the input is ray 3k of the set, its companions b and c are
+    3k + 1 and 3k + 2, neighbours[3k] = (3k + 1, 3k + 2) and the companions have no tube of their own (-1, -1).
+    With (u, v) = tube_frame(dir0) and d = dir0 / |dir0|:
+      delta_pos (metres):    b starts at pos0 + delta_pos u, c at pos0 + delta_pos v, so that the section at t = 0 is
+                             1/2 delta_pos^2 d;
+      delta_angle (radians): b starts along d cos(delta_angle) + u sin(delta_angle) (d turned about v), c along
+                             d cos(delta_angle) + v sin(delta_angle) (d turned about -u), scaled to |dir0|.
+    Either or both may be given, not neither.  The companions keep the ray's frequency."""
+    if delta_pos is None and delta_angle is None:
+        raise ValueError("tube_fan: give delta_pos (metres), delta_angle (radians) or both")
+    pos0, dir0, w0 = _f64(pos0).reshape(-1, 3), _f64(dir0).reshape(-1, 3), _f64(w0).reshape(-1)
+    n = len(w0)
+    if not (len(pos0) == len(dir0) == n):
+        raise ValueError("pos0, dir0 and w0 name %d, %d and %d rays" % (len(pos0), len(dir0), n))
+    u, v = tube_frame(dir0)
+    pos = np.repeat(pos0, 3, axis=0)
+    direction = np.repeat(dir0, 3, axis=0)
+    if delta_pos is not None:
+        pos[1::3] = pos0 + float(delta_pos) * u
+        pos[2::3] = pos0 + float(delta_pos) * v
+    if delta_angle is not None:
+        c, s = np.cos(float(delta_angle)), np.sin(float(delta_angle))
+        norm = np.sqrt((dir0 * dir0).sum(axis=1))[:, None]
+        direction[1::3] = dir0 * c + norm * s * u
+        direction[2::3] = dir0 * c + norm * s * v
+    neighbours = np.full((3 * n, 2), -1, dtype=np.int64)
+    neighbours[0::3, 0] = 3 * np.arange(n) + 1
+    neighbours[0::3, 1] = 3 * np.arange(n) + 2
+    return pos, direction, np.repeat(w0, 3), neighbours
 
 
 # ---- traced rays binned onto a grid: dwell time and power maps (include/srt.h) -------

@@ -1,7 +1,7 @@
 // srt_api_rows.hpp -- what is done with traced rows: hot-plasma damping along them (srt_damping.hpp), packing the rows a ray
-// kept (srt_pack_rows_device), what a packed row set must satisfy, said once for every entry point that takes one, and the three
-// post-processors of packed rows: surface crossings (srt_crossings.hpp), closest approaches (srt_approaches.hpp), binning onto a
-// grid (srt_binning.hpp).
+// kept (srt_pack_rows_device), what a packed row set must satisfy, said once for every entry point that takes one, and the four
+// post-processors of packed rows: surface crossings (srt_crossings.hpp), closest approaches (srt_approaches.hpp), ray-tube
+// sections (srt_tubes.hpp), binning onto a grid (srt_binning.hpp).
 // A part of srt_api.hip (srt_api_core.hpp).
 #pragma once
 #include "srt_api_core.hpp"
@@ -10,6 +10,7 @@
 #include "srt_crossings.hpp"
 #include "srt_binning.hpp"
 #include "srt_approaches.hpp"
+#include "srt_tubes.hpp"
 #include <hipcub/hipcub.hpp>
 
 // ---- the step after the path: hot-plasma damping along the kept rows (kernels: srt_damping.hpp) ----
@@ -423,6 +424,72 @@ extern "C" int srt_approaches(int nobs, const srt_observer *observers, int64_t n
         return srt_approaches_device(nobs, observers, nrays, d_off, d_rows, d_ev, d_meta, d_dist, capacity, d_count, nullptr);
       },
       nevents, event_rows, event_meta, event_dist);
+}
+
+// ---- ray tubes: the section a ray and two neighbours span, at every packed row (kernel and point functions: srt_tubes.hpp) ----
+extern "C" int srt_tubes_device(int64_t nrays, const int64_t *neighbours, const int64_t *d_offsets, const double *d_rows,
+                                double *d_section, int32_t *d_flag, void *stream) {
+  namespace tb = srt::tubes;
+  static_assert(sizeof(long long) == sizeof(int64_t), "int64");
+  char why[200];
+  if (tb::check_neighbours(nrays, (const long long *)neighbours, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_tubes_device: %s", why);
+  if (!d_section && !d_flag) return srt_set_error(SRT_EINVAL, "srt_tubes_device: both outputs (d_section and d_flag) are null");
+  const void *ptrs[4] = {d_offsets, d_rows, d_section, d_flag};
+  DeviceScope scope;
+  // (no events: no capacity to judge; the output that is there stands where the others pass their counter)
+  int rc = packed_rows_device("srt_tubes_device", nrays, d_offsets, d_section ? (const void *)d_section : (const void *)d_flag,
+                              "an output", nullptr, false, ptrs, 4, scope);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the one thing the host has to know: how many rows there are
+  long long total = 0;
+  HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  const char *refuse = packed_total_refusal(total, d_rows);
+  // (a single row is a centre row here, where the crossings need two for an interval)
+  if (!refuse && total == 1 && !d_rows) refuse = "row, and d_rows is null";
+  if (!refuse && total == 1 && !within_allocation(d_rows, (size_t)SRT_ROW * sizeof(double))) refuse = "row, more than the allocation of d_rows holds";
+  if (refuse) return srt_set_error(SRT_EINVAL, "srt_tubes_device: offsets[nrays] = %lld %s", total, refuse);
+  if (total == 0) return SRT_OK;
+  if ((d_section && !within_allocation(d_section, (size_t)total * 4 * sizeof(double))) ||
+      (d_flag && !within_allocation(d_flag, (size_t)total * sizeof(int32_t))))
+    return srt_set_error(SRT_EINVAL, "srt_tubes_device: an output has no room for offsets[nrays] = %lld rows", total);
+  // the neighbours go up as the approaches' observers do: a plain allocation, a synchronous copy, and a wait for the stream
+  // before it is freed
+  DevBuf<long long> d_nb;
+  HIP_OK(d_nb.alloc(nrays > 0 ? (size_t)nrays * 2 : 2));
+  HIP_OK(hipMemcpy(d_nb.p, neighbours, (size_t)nrays * 2 * sizeof(long long), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(tb::tubes_kernel<tb::BLOCK>, dim3(grid_blocks(total, tb::BLOCK)), dim3(tb::BLOCK), 0, st, srt::rows::light_speed(),
+                     (long long)nrays, (const long long *)d_offsets, total, d_rows, (const long long *)d_nb.p, d_section, d_flag);
+  const hipError_t e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(st); // (also on the error path: the neighbours go away when this returns)
+  HIP_OK(e);
+  HIP_OK(es);
+  return SRT_OK;
+}
+
+extern "C" int srt_tubes(int64_t nrays, const int64_t *neighbours, const int64_t *offsets, const double *rows, double *section,
+                         int32_t *flag) {
+  char why[200];
+  if (srt::tubes::check_neighbours(nrays, (const long long *)neighbours, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_tubes: %s", why);
+  if (!section && !flag) return srt_set_error(SRT_EINVAL, "srt_tubes: both outputs (section and flag) are null");
+  const int64_t total = packed_rows_host("srt_tubes", nrays, offsets, rows);
+  if (total < 0) return SRT_EINVAL;
+  DeviceScope srt_iscope_;
+  int rc = srt_iscope_.enter_default();
+  if (rc) return rc;
+  if (total == 0) return SRT_OK;
+  DevBuf<double> d_rows, d_section;
+  DevBuf<int64_t> d_off;
+  DevBuf<int32_t> d_flag;
+  if ((rc = upload_packed(nrays, offsets, rows, total, d_off, d_rows))) return rc;
+  if (section) HIP_OK(d_section.alloc((size_t)total * 4));
+  if (flag) HIP_OK(d_flag.alloc((size_t)total));
+  if ((rc = srt_tubes_device(nrays, neighbours, d_off.p, d_rows.p, d_section.p, d_flag.p, nullptr))) return rc;
+  HIP_OK(hipDeviceSynchronize());
+  if (section) HIP_OK(hipMemcpy(section, d_section.p, (size_t)total * 4 * sizeof(double), hipMemcpyDeviceToHost));
+  if (flag) HIP_OK(hipMemcpy(flag, d_flag.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return SRT_OK;
 }
 
 // ---- traced rays binned onto a grid (kernel and point functions: srt_binning.hpp) ----

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <array>
 #include <future>
+#include <map>
 #include <memory>
 #include <string>
 #include <thread>
@@ -483,6 +484,69 @@ static int mode_approach() {
   CHECK(srt_approaches_file_write(aout.c_str(), nev, evray.data(), meta, dist, ev));
   printf(" %lld rays, %lld records, %zu observers, %lld approaches\n", (long long)ray.n, (long long)ray.nrec, obs.size(), (long long)nev);
   srt_free(ev), srt_free(meta), srt_free(dist);
+  return 0;
+}
+
+// ours: --tube_in=<existing .ray file> --tube_neighbours=<file> --tube_out=<file>: the sections of the ray tubes of the second
+// file (include/srt.h, "ray tubes") at every record of their centre rays, without tracing.  Whatever is wrong with the three
+// flags or the two input files is refused by name with exit code 2.
+static int mode_tube() {
+  std::string tin, tnb, tout;
+  need(getopt_named("tube_in", tin), "tube_in");
+  need(getopt_named("tube_neighbours", tnb), "tube_neighbours");
+  need(getopt_named("tube_out", tout), "tube_out");
+  int device = 0;
+  get_int("device", device);
+  // one tube per line, list-directed: centre b c, the ray numbers of the .ray file
+  std::vector<std::array<double, 5>> lines;
+  const int bad = read_number_lines(tnb, 3, 3, lines);
+  if (bad < 0) {
+    fprintf(stderr, "raytracer: --tube_neighbours: cannot open %s\n", tnb.c_str());
+    return 2;
+  }
+  if (bad > 0) {
+    fprintf(stderr, "raytracer: --tube_neighbours: %s, line %d: expected `centre b c` (three ray numbers)\n", tnb.c_str(), bad);
+    return 2;
+  }
+  RayFile ray(tin);
+  if (ray.n < 0) {
+    fprintf(stderr, "raytracer: --tube_in: %s\n", srt_last_error());
+    return 2;
+  }
+  std::map<int64_t, int64_t> index; // ray number -> ray of the file
+  for (int64_t i = 0; i < ray.n; ++i) index[ray.raynum[i]] = i;
+  std::vector<int64_t> nb(ray.n > 0 ? (size_t)ray.n * 2 : 2, -1);
+  for (size_t k = 0; k < lines.size(); ++k) {
+    int64_t idx[3];
+    for (int c = 0; c < 3; ++c) {
+      const double v = lines[k][c];
+      const auto it = v == std::floor(v) && std::fabs(v) < 1e15 ? index.find((int64_t)v) : index.end();
+      if (it == index.end()) {
+        fprintf(stderr, "raytracer: --tube_neighbours: %s, tube %zu: %s holds no ray number %.17g\n", tnb.c_str(), k + 1, tin.c_str(), v);
+        return 2;
+      }
+      idx[c] = it->second;
+    }
+    if (nb[2 * idx[0]] != -1) {
+      fprintf(stderr, "raytracer: --tube_neighbours: %s, tube %zu: centre %lld is listed twice\n", tnb.c_str(), k + 1, (long long)ray.raynum[idx[0]]);
+      return 2;
+    }
+    if (idx[1] == idx[2] || idx[1] == idx[0] || idx[2] == idx[0]) {
+      fprintf(stderr, "raytracer: --tube_neighbours: %s, tube %zu: a tube takes three different rays\n", tnb.c_str(), k + 1);
+      return 2;
+    }
+    nb[2 * idx[0]] = idx[1], nb[2 * idx[0] + 1] = idx[2];
+  }
+  std::vector<double> section((size_t)ray.nrec * 4 + 4);
+  std::vector<int32_t> flag((size_t)ray.nrec + 1);
+  if (ray.nrec > 0) { // (no record: nothing to ask a device for)
+    CHECK(srt_init(device));
+    CHECK(srt_tubes(ray.n, nb.data(), ray.offsets.data(), ray.rows, section.data(), flag.data()));
+  }
+  CHECK(srt_tubes_file_write(tout.c_str(), ray.n > 0 ? ray.n : 0, ray.raynum, ray.offsets.data(), ray.rows, section.data(), flag.data()));
+  long long ok = 0, with = 0;
+  for (int64_t j = 0; j < ray.nrec; ++j) ok += flag[j] == 0, with += flag[j] != 1;
+  printf(" %lld rays, %lld records, %zu tubes, %lld sections (%lld ok)\n", (long long)ray.n, (long long)ray.nrec, lines.size(), with, ok);
   return 0;
 }
 
@@ -1037,6 +1101,11 @@ int main(int argc, char **argv) {
          "           file holds one `x y z radius` per line (SM metres; an approach is reported when it comes within the radius);\n"
          "           one record per event: raynum, observer, interval, 0 (4 i10), then the distance and t, pos, vprel, vgrel, n,\n"
          "           B0, Ns (21 es24.15e3)\n"
+         "           --tube_in=<.ray file> --tube_neighbours=<file> --tube_out=<file> [--device=N]: the cross-section of ray tubes\n"
+         "           (geometric spreading) at every record of their centre rays; the neighbours file holds one tube per line,\n"
+         "           `centre b c`, as ray numbers of the .ray file; a neighbour is taken at the centre record's time on the cubic\n"
+         "           Hermite curve through its own records; one record per centre record: raynum, record, flag (3 i10), then t, the\n"
+         "           area vector (m^2) and its component along the group velocity (5 es24.15e3)\n"
          "           --bin_in=<.ray file> --bin_axes=<file> --bin_out=<file> [--bin_nsub=8] [--bin_quantum=9.313225746154785e-10]\n"
          "           [--device=N]: the dwell-time map of the rays of an existing file: every interval of consecutive records is cut\n"
          "           into bin_nsub pieces on the cubic Hermite curve, each deposits its duration into the cell of its midpoint, in\n"
@@ -1052,6 +1121,7 @@ int main(int argc, char **argv) {
   if (have_flag("damping_in")) return mode_damping_in();
   // (one flag of a post-processor's three selects it; the mode then names the ones that are missing)
   if (have_flag("approach_in") || have_flag("approach_observers") || have_flag("approach_out")) return mode_approach();
+  if (have_flag("tube_in") || have_flag("tube_neighbours") || have_flag("tube_out")) return mode_tube();
   if (have_flag("crossings_in") || have_flag("crossings_surfaces") || have_flag("crossings_out")) return mode_crossings();
   if (have_flag("bin_in") || have_flag("bin_axes") || have_flag("bin_out")) return mode_bin();
   return mode_trace();

@@ -900,6 +900,42 @@ extern "C" int srt_approaches_file_write(const char *path, int64_t nevents, cons
   return write_event_records("srt_approaches_file_write", path, nevents, raynum, event_meta, event_dist, event_rows);
 }
 
+// tubes file: one record per packed row whose flag is not 1, (3 i10, 5 es24.15e3): raynum, row + 1 (among the ray's kept rows),
+// flag, t, the section
+extern "C" int srt_tubes_file_write(const char *path, int64_t nrays, const int64_t *raynum, const int64_t *offsets, const double *rows,
+                                    const double *section, const int32_t *flag) {
+  if (!path || nrays < 0 || !offsets || (nrays > 0 && !raynum)) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: null argument");
+  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
+  for (int64_t r = 0; r < nrays; ++r)
+    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: offsets decrease at ray %lld", (long long)r);
+  if (offsets[nrays] > 0 && (!rows || !section || !flag)) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: null argument");
+  for (int64_t r = 0; r < nrays; ++r)
+    if (raynum[r] < 0 || raynum[r] > 9999999999ll)
+      return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: ray number %lld of ray %lld does not fit the record's i10 field",
+                           (long long)raynum[r], (long long)r);
+  FILE *fp = fopen(path, "w");
+  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
+  std::vector<char> big(1 << 22);
+  setvbuf(fp, big.data(), _IOFBF, big.size());
+  const size_t L = 30 + 5 * 24 + 1;
+  char rec[L + 8];
+  for (int64_t r = 0; r < nrays; ++r)
+    for (int64_t j = offsets[r]; j < offsets[r + 1]; ++j) {
+      if (flag[j] == 1) continue;
+      char head[48];
+      snprintf(head, sizeof head, "%10lld%10lld%10d", (long long)raynum[r], (long long)(j - offsets[r] + 1), (int)flag[j]);
+      memcpy(rec, head, 30);
+      char *q = rec + 30;
+      put_es24(rows[(size_t)j * SRT_ROW], q);
+      q += 24;
+      for (int c = 0; c < 4; ++c, q += 24) put_es24(section[(size_t)j * 4 + c], q);
+      *q = '\n';
+      fwrite(rec, 1, L, fp);
+    }
+  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
+  return SRT_OK;
+}
+
 // ---- bin file: a map of srt_bin_rays as text (include/srt.h) ----
 // the grid's soundness is srt_binning.hpp's prepare(), the host half of that header; -> 0 and *ncells, or -1 and `why`
 static int bin_file_cells(const srt_bin_params *params, int64_t *ncells, char *why, size_t whylen) {

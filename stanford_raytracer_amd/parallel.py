@@ -133,6 +133,27 @@ def approaches_device(packed, offsets, observers, capacity=None, stream=None):
     return _events_device(call, offsets, capacity, stream, True)
 
 
+def tubes_device(packed, offsets, neighbours, stream=None):
+    """srt_tubes_device on torch CUDA tensors (packed[>= offsets[n], 20], offsets[n + 1] as pack_rows_device returns them;
+    neighbours[n, 2] int64 on the host, as api.tube_fan returns them) -> (section[rows of packed, 4] float64, flag[rows of packed]
+    int32) on the device: row j of both belongs to packed row j, and the rows beyond offsets[n] keep NaN and flag 1.  The number
+    of rows stays on the device; the library waits for its own pass (include/srt.h)."""
+    import torch
+
+    from . import api
+
+    n = offsets.shape[0] - 1
+    nb = api.neighbour_table(neighbours, n)
+    dev = offsets.device
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    cap = max(packed.shape[0], 1)
+    section = torch.full((cap, 4), float("nan"), dtype=torch.float64, device=dev)
+    flag = torch.ones(cap, dtype=torch.int32, device=dev)
+    api._check(api.lib().srt_tubes_device(n, nb.ctypes.data_as(api.C.POINTER(api.C.c_int64)), offsets.data_ptr(), packed.data_ptr(),
+                                          section.data_ptr(), flag.data_ptr(), st.cuda_stream))
+    return section, flag
+
+
 def crossings_device(packed, offsets, surfaces, capacity=None, stream=None):
     """srt_crossings_device on torch CUDA tensors (packed[>= offsets[n], 20], offsets[n + 1] as pack_rows_device returns them)
     -> (event_rows[capacity, 20], meta[capacity, 4] int32, count[1] int64), all on the device; the first min(count, capacity)
