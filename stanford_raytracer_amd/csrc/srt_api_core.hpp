@@ -1,6 +1,7 @@
 // srt_api_core.hpp -- what every unit of the C ABI's host side stands on: the error text and HIP_OK, DevBuf (the owner of device
 // memory), device selection and DeviceScope, struct srt_model, with_model (the one place that turns a kind number into a type),
-// SRT_MODEL_SCOPE / ensure_model, and the small helpers of the later units: upload, download, grid_blocks, within_allocation.
+// SRT_MODEL_SCOPE / ensure_model, and the small helpers of the later units: upload, download, grid_blocks, stride_blocks,
+// within_allocation, with_cub_temp.
 //
 // The srt_api_*.hpp headers are the parts of ONE translation unit, srt_api.hip, and are not for inclusion anywhere else: this
 // one owns the names they share at global scope (`using namespace srt;` and the three macros).
@@ -331,6 +332,13 @@ static unsigned grid_blocks(long long n, long long per) {
   return (unsigned)(blocks < 65536 ? blocks : 65536);
 }
 
+// the blocks of 256 threads of a grid-stride launch over n items with the older cap of 65535 * 4 (the interp grids' kernels;
+// grid_blocks caps elsewhere and is not this function)
+static int stride_blocks(size_t n) {
+  const size_t blocks = (n + 255) / 256;
+  return (int)(blocks < 65535 * 4 ? blocks : 65535 * 4);
+}
+
 // does [q, q + bytes) lie inside the allocation q points into?  (true when the runtime cannot say)
 static bool within_allocation(const void *q, size_t bytes) {
   hipDeviceptr_t base = nullptr;
@@ -340,4 +348,20 @@ static bool within_allocation(const void *q, size_t bytes) {
     return true;
   }
   return (const char *)q + bytes <= (const char *)base + size;
+}
+
+// Temporary storage around one hipCUB call, from the stream-ordered allocator (the callers sit on the multi-GPU gather's timed
+// path): cub(tmp, bytes) is the call; it is asked for its size with tmp = null, then run, and the storage is freed behind it on
+// `st`, also on the error path.  (srt_crossings_device and srt_approaches_device keep plain allocations, for their own reason.)
+template <class Cub>
+static int with_cub_temp(hipStream_t st, Cub &&cub) {
+  size_t need = 0;
+  HIP_OK(cub((void *)nullptr, need));
+  void *tmp = nullptr;
+  HIP_OK(hipMallocAsync(&tmp, need ? need : 16, st));
+  const hipError_t e = cub(tmp, need);
+  const hipError_t ef = hipFreeAsync(tmp, st); // (also on the error path)
+  HIP_OK(e);
+  HIP_OK(ef);
+  return SRT_OK;
 }

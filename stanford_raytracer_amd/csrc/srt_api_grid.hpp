@@ -157,7 +157,8 @@ static int resolve_layout(int nspec, int nx, int ny, int nz, int layout, int *ou
 }
 
 // FD derivatives (unless given) + coefficient expansion (or the node table: `layout`, SRT_INTERP_EXPANDED or _NODES) + model
-// object, from the 8 arrays already on the device.
+// object, from the 8 arrays already on the device.  Only the table's kernel and what the model struct holds branch by layout:
+// the axes, the owner (ModelPtr) and the tail (model_hand_over, srt_api_model.hpp) are common.
 // arr[0] = F; arr[1..7] = derivative blocks (contents ignored when !have_derivs).  The arrays are freed here, before the model
 // is made.
 static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const double bounds[6], const double *qs,
@@ -174,7 +175,7 @@ static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const do
   hipError_t e = hipSuccess;
   if (!have_derivs) {
     for (int a = 1; a < 8 && e == hipSuccess; ++a) e = hipMemset(arr[a].p, 0, n * sizeof(double));
-    int blocks = (int)((n + 255) / 256 < 65535 * 4 ? (n + 255) / 256 : 65535 * 4);
+    const int blocks = stride_blocks(n);
     auto fd = [&](int src, int dst, int axis, double h) {
       hipLaunchKernelGGL(fd_axis_kernel, dim3(blocks), dim3(256), 0, 0, g, (const double *)arr[src].p, arr[dst].p, axis, h);
     };
@@ -191,72 +192,45 @@ static int interp_from_device_arrays(int nspec, int nx, int ny, int nz, const do
   if (e == hipSuccess) e = coef.alloc(as_nodes ? n * 8 : ncell * nspec * 64);
   if (e != hipSuccess)
     return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "interp model setup: %s", hipGetErrorString(e));
-  if (as_nodes) {
-    ArrPtrs ap;
-    for (int a = 0; a < 8; ++a) ap.a[a] = arr[a].p;
-    const int blocks = (int)((n + 255) / 256 < 65535 * 4 ? (n + 255) / 256 : 65535 * 4);
-    hipLaunchKernelGGL(build_nodes_kernel, dim3(blocks), dim3(256), 0, 0, ap, dx, dy, dz, coef.p, n);
-    e = hipDeviceSynchronize();
-    for (auto &b : arr) b.release();
-    if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "node table build failed: %s", hipGetErrorString(e));
-    srt_model *m = new srt_model;
-    m->kind = KIND_INTERP_NODES;
-    m->nspec = nspec;
-    m->d_coef.swap(coef);
-    m->device_bytes = (int64_t)(n * 8 * sizeof(double));
-    InterpNodesModel &nm = m->as<InterpNodesModel>();
-    nm.nodes = m->d_coef.p;
-    nm.nspec = nspec;
-    nm.ax = Axis{bounds[0], dx, 1.0 / dx, nx};
-    nm.ay = Axis{bounds[2], dy, 1.0 / dy, ny};
-    nm.az = Axis{bounds[4], dz, 1.0 / dz, nz};
-    // the launch-cell ray order (srt_trace_batch_device) takes its keys from the axes in InterpModel's form, on both layouts
-    InterpModel &im = m->as<InterpModel>();
-    im.coef = nullptr;
-    im.nspec = nspec;
-    im.ax = nm.ax, im.ay = nm.ay, im.az = nm.az;
-    fill_common(m->cm, nspec, qs, ms, yearday, msec);
-    int rc = model_finish(m);
-    if (!rc && m->d_axes.alloc(1) != hipSuccess) rc = srt_set_error(SRT_ENOMEM, "hipMalloc failed");
-    if (!rc && hipMemcpy(m->d_axes.p, &im, sizeof im, hipMemcpyHostToDevice) != hipSuccess)
-      rc = srt_set_error(SRT_EDEVICE, "upload of the axes failed");
-    if (rc) {
-      srt_model_destroy(m);
-      return rc;
-    }
-    *out = m;
-    return SRT_OK;
-  }
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_ptr), TRI_PTR, sizeof TRI_PTR);
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_col), TRI_COL, sizeof TRI_COL);
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_val), TRI_VAL, sizeof TRI_VAL);
   ArrPtrs ap;
   for (int a = 0; a < 8; ++a) ap.a[a] = arr[a].p;
-  long long npairs = (long long)ncell * nspec;
-  int blocks = (int)(npairs < 262144 ? npairs : 262144);
-  hipLaunchKernelGGL(build_coeffs_kernel, dim3(blocks), dim3(64), 0, 0, g, ap, dx, dy, dz, coef.p, npairs);
+  if (as_nodes) {
+    hipLaunchKernelGGL(build_nodes_kernel, dim3(stride_blocks(n)), dim3(256), 0, 0, ap, dx, dy, dz, coef.p, n);
+  } else {
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_ptr), TRI_PTR, sizeof TRI_PTR);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_col), TRI_COL, sizeof TRI_COL);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(c_tri_val), TRI_VAL, sizeof TRI_VAL);
+    long long npairs = (long long)ncell * nspec;
+    int blocks = (int)(npairs < 262144 ? npairs : 262144);
+    hipLaunchKernelGGL(build_coeffs_kernel, dim3(blocks), dim3(64), 0, 0, g, ap, dx, dy, dz, coef.p, npairs);
+  }
   e = hipDeviceSynchronize();
   for (auto &b : arr) b.release();
-  if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "coefficient build failed: %s", hipGetErrorString(e));
-  srt_model *m = new srt_model;
-  m->kind = KIND_INTERP;
-  m->nspec = nspec;
+  if (e != hipSuccess) return srt_set_error(SRT_EDEVICE, "%s build failed: %s", as_nodes ? "node table" : "coefficient", hipGetErrorString(e));
+  // the model object: the table, and the axes in InterpModel's form on both layouts (the launch-cell ray order,
+  // srt_trace_batch_device, takes its keys from them)
+  ModelPtr m = new_model(as_nodes ? KIND_INTERP_NODES : KIND_INTERP, nspec);
   m->d_coef.swap(coef);
-  m->device_bytes = (int64_t)(ncell * nspec * 64 * sizeof(double));
+  m->device_bytes = (int64_t)(m->d_coef.cap * sizeof(double));
   InterpModel &im = m->as<InterpModel>();
-  im.coef = m->d_coef.p;
+  im.coef = as_nodes ? nullptr : m->d_coef.p;
   im.nspec = nspec;
   im.ax = Axis{bounds[0], dx, 1.0 / dx, nx};
   im.ay = Axis{bounds[2], dy, 1.0 / dy, ny};
   im.az = Axis{bounds[4], dz, 1.0 / dz, nz};
-  fill_common(m->cm, nspec, qs, ms, yearday, msec);
-  int rc = model_finish(m);
-  if (rc) {
-    srt_model_destroy(m);
-    return rc;
+  if (as_nodes) {
+    InterpNodesModel &nm = m->as<InterpNodesModel>();
+    nm.nodes = m->d_coef.p;
+    nm.nspec = nspec;
+    nm.ax = im.ax, nm.ay = im.ay, nm.az = im.az;
   }
-  *out = m;
-  return SRT_OK;
+  fill_common(m->cm, nspec, qs, ms, yearday, msec);
+  return model_hand_over(m, out, [&](srt_model *p) -> int { // (the node-table layout keeps the axes on the device as well)
+    if (!as_nodes) return SRT_OK;
+    if (p->d_axes.alloc(1) != hipSuccess) return srt_set_error(SRT_ENOMEM, "hipMalloc failed");
+    if (hipMemcpy(p->d_axes.p, &im, sizeof im, hipMemcpyHostToDevice) != hipSuccess) return srt_set_error(SRT_EDEVICE, "upload of the axes failed");
+    return SRT_OK;
+  });
 }
 
 static int alloc_grid_arrays(size_t n, DevBuf<double> (&arr)[8]) {

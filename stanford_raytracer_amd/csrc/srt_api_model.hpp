@@ -1,6 +1,7 @@
 // srt_api_model.hpp -- a model handle's life apart from the interp grids: the constants every model carries (fill_common), the
 // device copies and events (model_finish), destroy and trim, the field options (IGRF table, T04_s parameters), the srt_model_*
-// getters, and the constructors of the Ngo, Ngo3d, simple3d, AT64ThCh and scattered models.  Also the scattered model's scratch
+// getters, and the constructors of the Ngo, Ngo3d, simple3d, AT64ThCh and scattered models: a ModelPtr owns a model under
+// construction and model_hand_over is every constructor's tail (the interp ones' too).  Also the scattered model's scratch
 // policy, which the per-point calls (srt_api_points.hpp) and the trace launch (srt_api_trace.hpp) share.
 // A part of srt_api.hip (srt_api_core.hpp).
 #pragma once
@@ -84,6 +85,30 @@ extern "C" int srt_model_trim(srt_model *m) {
   }
   m->io.release();
   return SRT_OK;
+}
+// A model under construction: destroyed with srt_model_destroy, which takes a half-built handle (null events are skipped, empty
+// DevBufs free nothing), unless model_hand_over gives it to the caller.
+struct ModelDestroy {
+  void operator()(srt_model *m) const { srt_model_destroy(m); }
+};
+using ModelPtr = std::unique_ptr<srt_model, ModelDestroy>;
+static ModelPtr new_model(int kind, int nspec) {
+  ModelPtr m(new srt_model);
+  m->kind = kind;
+  m->nspec = nspec;
+  return m;
+}
+// every constructor's tail: the device copies and events, then what the kind needs behind them (`then`), then the handle is the
+// caller's
+template <class Then>
+static int model_hand_over(ModelPtr &m, srt_model **out, Then &&then) {
+  int rc = model_finish(m.get());
+  if (rc || (rc = then(m.get()))) return rc;
+  *out = m.release();
+  return SRT_OK;
+}
+static int model_hand_over(ModelPtr &m, srt_model **out) {
+  return model_hand_over(m, out, [](srt_model *) -> int { return SRT_OK; });
 }
 // geopack's RECALC_08 for the handle's date: coefficients, GEO->GSM matrix, the adapters' PS and geopack's own PSI
 static int load_field_table(srt_model *m, const char *igrf_coeff_file) {
@@ -184,20 +209,13 @@ static int ngo_readinput(const char *configfile, NgoModel &g) {
   return SRT_OK;
 }
 
-// species constants of both Ngo adapters (ngo_dens_model_adapter.f95:136-138, ngo_3d_dens_model_adapter.f95:173-175), the
-// field tail's date, and the device copies
-static int ngo_finish(srt_model *m, int yearday, int msec, srt_model **out) {
+// electrons, H+, He+, O+: the species constants of both Ngo adapters (ngo_dens_model_adapter.f95:136-138,
+// ngo_3d_dens_model_adapter.f95:173-175) and of simple3d's (:813-815), with the field tail's date
+static void fill_common_four_species(Common &cm, int yearday, int msec) {
   const double e_ = 1.602e-19;
   double qs[4] = {e_ * -1.0, e_, e_, e_};
   double ms[4] = {9.10938188e-31, 1.6726e-27, 4.0 * 1.6726e-27, 16.0 * 1.6726e-27};
-  fill_common(m->cm, 4, qs, ms, yearday, msec);
-  const int rc = model_finish(m);
-  if (rc) {
-    srt_model_destroy(m);
-    return rc;
-  }
-  *out = m;
-  return SRT_OK;
+  fill_common(cm, 4, qs, ms, yearday, msec);
 }
 
 extern "C" int srt_model_create_ngo(const char *configfile, int yearday, int msec, srt_model **out) {
@@ -205,15 +223,10 @@ extern "C" int srt_model_create_ngo(const char *configfile, int yearday, int mse
   DeviceScope srt_iscope_;
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
-  srt_model *m = new srt_model;
-  m->kind = KIND_NGO;
-  m->nspec = 4;
-  rc = ngo_readinput(configfile, m->as<NgoModel>());
-  if (rc) {
-    delete m;
-    return rc;
-  }
-  return ngo_finish(m, yearday, msec, out);
+  ModelPtr m = new_model(KIND_NGO, 4);
+  if ((rc = ngo_readinput(configfile, m->as<NgoModel>()))) return rc;
+  fill_common_four_species(m->cm, yearday, msec);
+  return model_hand_over(m, out);
 }
 
 // ---- ngo3d: the Ngo model with the plasmapause of each evaluated point from bulge(MLT, Kp) (srt_ngo3d.hpp) ------
@@ -225,19 +238,14 @@ extern "C" int srt_model_create_ngo3d(const char *configfile, double kp, int fix
   DeviceScope srt_iscope_;
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
-  srt_model *m = new srt_model;
-  m->kind = KIND_NGO3D;
-  m->nspec = 4;
+  ModelPtr m = new_model(KIND_NGO3D, 4);
   Ngo3dModel &g = m->as<Ngo3dModel>();
-  rc = ngo_readinput(configfile, g.ngo); // ane0 is normalised with the file's lk (readinput runs once, at setup)
-  if (rc) {
-    delete m;
-    return rc;
-  }
+  if ((rc = ngo_readinput(configfile, g.ngo))) return rc; // ane0 is normalised with the file's lk (readinput runs once, at setup)
   g.kp = kp;
   g.fixed_mlt = fixed_MLT;
   g.mlt = MLT;
-  return ngo_finish(m, yearday, msec, out);
+  fill_common_four_species(m->cm, yearday, msec);
+  return model_hand_over(m, out);
 }
 
 // ---- simple3d: closed form, nothing but a handful of constants (srt_simple3d.hpp) -------------------
@@ -248,27 +256,15 @@ extern "C" int srt_model_create_simple3d(double kp, int fixed_MLT, double MLT, i
   DeviceScope srt_iscope_;
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
-  srt_model *m = new srt_model;
-  m->kind = KIND_SIMPLE3D;
-  m->nspec = 4;
+  ModelPtr m = new_model(KIND_SIMPLE3D, 4);
   auto &c = m->as<Simple3dModel>().c;
   c.kp = kp;
   c.year = yearday / 1000; // iyear = itime(1)/1000, doy = itime(1) - iyear*1000 (:743-744)
   c.doy = yearday - c.year * 1000;
   c.fixed_mlt = fixed_MLT;
   c.mlt = MLT;
-  // the adapter's own species constants (:813-815)
-  const double e_ = 1.602e-19;
-  double qs[4] = {e_ * -1.0, e_, e_, e_};
-  double ms[4] = {9.10938188e-31, 1.6726e-27, 4.0 * 1.6726e-27, 16.0 * 1.6726e-27};
-  fill_common(m->cm, 4, qs, ms, yearday, msec);
-  rc = model_finish(m);
-  if (rc) {
-    srt_model_destroy(m);
-    return rc;
-  }
-  *out = m;
-  return SRT_OK;
+  fill_common_four_species(m->cm, yearday, msec);
+  return model_hand_over(m, out);
 }
 
 // ---- at64thch: closed form around one field-line trace per point (srt_at64thch.hpp, srt_fieldline.hpp) ----------
@@ -280,9 +276,7 @@ extern "C" int srt_model_create_at64thch(int gcpm_kp, const double parmod[10], c
   DeviceScope srt_iscope_;
   int rc = srt_iscope_.enter_default();
   if (rc) return rc;
-  srt_model *m = new srt_model;
-  m->kind = KIND_AT64THCH;
-  m->nspec = 3;
+  ModelPtr m = new_model(KIND_AT64THCH, 3);
   m->as<At64ThChModel>().gcpm_kp = gcpm_kp;
   // the adapter's own species constants (:272-273): electrons, O+, H+
   const double e_ = 1.602e-19;
@@ -292,12 +286,8 @@ extern "C" int srt_model_create_at64thch(int gcpm_kp, const double parmod[10], c
   // the trace uses T04_s and IGRF whatever the field options say: the table and parmod are part of the model
   for (int i = 0; i < 10; ++i) m->cm.fld.parmod[i] = (float)parmod[i]; // real(parmod), decision 1
   m->have_parmod = true;
-  if ((rc = load_field_table(m, igrf_coeff_file)) || (rc = model_finish(m)) || (rc = upload_constants(m))) {
-    srt_model_destroy(m);
-    return rc;
-  }
-  *out = m;
-  return SRT_OK;
+  if ((rc = load_field_table(m.get(), igrf_coeff_file))) return rc;
+  return model_hand_over(m, out, upload_constants);
 }
 
 extern "C" int srt_model_create_scattered_file(const char *ptsfile, int yearday, int msec, double window_scale,
@@ -330,9 +320,7 @@ extern "C" int srt_model_create_scattered_file_root(const char *ptsfile, int yea
   }
   if (!srt_host::build_scattered(ptsfile, window_scale, h, err, 1.0 + bmargin, (long long)root_sample))
     return srt_set_error(SRT_EIO, "%s: %s", ptsfile, err.c_str());
-  srt_model *m = new srt_model;
-  m->kind = KIND_SCATTERED;
-  m->nspec = h.nspec;
+  ModelPtr m = new_model(KIND_SCATTERED, h.nspec);
   std::vector<double> xyz(3 * (size_t)h.npts);
   for (size_t i = 0; i < (size_t)h.npts; ++i)
     for (int c = 0; c < 3; ++c) xyz[(size_t)c * h.npts + i] = h.pts[8 * i + c];
@@ -342,10 +330,8 @@ extern "C" int srt_model_create_scattered_file_root(const char *ptsfile, int yea
   if (e == hipSuccess) e = hipMemcpy(m->d_xyz.p, xyz.data(), xyz.size() * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->d_pts.p, h.pts.data(), h.pts.size() * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->d_cells.p, h.cell_start.data(), h.cell_start.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    srt_model_destroy(m);
+  if (e != hipSuccess)
     return srt_set_error(e == hipErrorOutOfMemory ? SRT_ENOMEM : SRT_EDEVICE, "scattered model upload: %s", hipGetErrorString(e));
-  }
   m->device_bytes = (int64_t)((h.pts.size() + xyz.size()) * sizeof(double) + h.cell_start.size() * sizeof(int));
   ScatteredModel &s = m->as<ScatteredModel>();
   s.pts = m->d_pts.p;
@@ -366,13 +352,7 @@ extern "C" int srt_model_create_scattered_file_root(const char *ptsfile, int yea
   s.exact = exact;
   s.npts = h.npts;
   fill_common(m->cm, h.nspec, h.qs, h.ms, yearday, msec);
-  rc = model_finish(m);
-  if (rc) {
-    srt_model_destroy(m);
-    return rc;
-  }
-  *out = m;
-  return SRT_OK;
+  return model_hand_over(m, out);
 }
 
 // a scratch allocation of the scattered model was refused: say so ONCE per model (the launch still runs -- without staging

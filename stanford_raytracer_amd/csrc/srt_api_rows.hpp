@@ -1,7 +1,8 @@
 // srt_api_rows.hpp -- what is done with traced rows: hot-plasma damping along them (srt_damping.hpp), packing the rows a ray
 // kept (srt_pack_rows_device), what a packed row set must satisfy, said once for every entry point that takes one, and the four
 // post-processors of packed rows: surface crossings (srt_crossings.hpp), closest approaches (srt_approaches.hpp), ray-tube
-// sections (srt_tubes.hpp), binning onto a grid (srt_binning.hpp).
+// sections (srt_tubes.hpp), binning onto a grid (srt_binning.hpp).  The device forms share fetch_packed_total and
+// packed_total_refused; the two event calls also event_rows_total and event_outputs_fit.
 // A part of srt_api.hip (srt_api_core.hpp).
 #pragma once
 #include "srt_api_core.hpp"
@@ -154,14 +155,10 @@ extern "C" int srt_pack_rows_device(int32_t slots, int32_t outputper, int64_t nr
   static_assert(sizeof(long long) == sizeof(int64_t), "int64");
   auto counts = hipcub::TransformInputIterator<long long, KeptRows, hipcub::CountingInputIterator<long long>>(
       hipcub::CountingInputIterator<long long>(0), KeptRows{d_nrows, outputper, slots});
-  size_t need = 0;
-  HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, (long long *)d_offsets, (int)nrays, st));
-  void *tmp = nullptr;
-  HIP_OK(hipMallocAsync(&tmp, need ? need : 16, st));
-  hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, need, counts, (long long *)d_offsets, (int)nrays, st);
-  const hipError_t ef = hipFreeAsync(tmp, st); // (also on the error path)
-  HIP_OK(e);
-  HIP_OK(ef);
+  if ((rc = with_cub_temp(st, [&](void *tmp, size_t &bytes) {
+         return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, counts, (long long *)d_offsets, (int)nrays, st);
+       })))
+    return rc;
   // offsets[nrays] = offsets[nrays-1] + kept(nrays-1)
   hipLaunchKernelGGL(pack_total_kernel, dim3(1), dim3(1), 0, st, KeptRows{d_nrows, outputper, slots}, (long long)nrays, (long long *)d_offsets);
   if (capacity_rows > 0)
@@ -214,6 +211,29 @@ static const char *packed_total_refusal(long long total, const double *d_rows) {
   if (total >= 2 && !within_allocation(d_rows, (size_t)total * SRT_ROW * sizeof(double))) return "rows, more than the allocation of d_rows holds";
   return nullptr;
 }
+static int packed_total_refused(const char *who, long long total, const char *refuse) { return srt_set_error(SRT_EINVAL, "%s: offsets[nrays] = %lld %s", who, total, refuse); }
+// the one thing the host has to know, how many rows there are: an 8-byte copy behind the work on `st`, and a wait for it
+static int fetch_packed_total(int64_t nrays, const int64_t *d_offsets, hipStream_t st, long long *total) {
+  HIP_OK(hipMemcpyAsync(total, d_offsets + nrays, sizeof *total, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return SRT_OK;
+}
+// The front of an event call's device form behind packed_rows_device: the total, its refusal, and -- fewer than two rows make no
+// interval -- a count of zero.  The caller goes on only when this answers SRT_OK with *total >= 2.
+static int event_rows_total(const char *who, int64_t nrays, const int64_t *d_offsets, const double *d_rows, int64_t *d_count,
+                            hipStream_t st, long long *total) {
+  if (const int rc = fetch_packed_total(nrays, d_offsets, st, total)) return rc;
+  if (const char *refuse = packed_total_refusal(*total, d_rows)) return packed_total_refused(who, *total, refuse);
+  if (*total < 2) HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
+  return SRT_OK;
+}
+// ... and the room its outputs have for `capacity` events of so many bytes each
+static int event_outputs_fit(const char *who, int64_t capacity, std::initializer_list<std::pair<const void *, size_t>> outputs) {
+  for (const auto &o : outputs)
+    if (capacity > 0 && !within_allocation(o.first, (size_t)capacity * o.second))
+      return srt_set_error(SRT_EINVAL, "%s: an output has no room for capacity = %lld events", who, (long long)capacity);
+  return SRT_OK;
+}
 
 // ---- surface crossings along packed rows (kernels and point functions: srt_crossings.hpp) ----
 extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int64_t nrays, const int64_t *d_offsets,
@@ -231,19 +251,9 @@ extern "C" int srt_crossings_device(int nsurf, const srt_surface *surfaces, int6
                               capacity > 0 && (!d_event_rows || !d_event_meta), ptrs, 5, scope);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the one thing the host has to know: how many rows there are
   long long total = 0;
-  HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  if (const char *refuse = packed_total_refusal(total, d_rows))
-    return srt_set_error(SRT_EINVAL, "srt_crossings_device: offsets[nrays] = %lld %s", total, refuse);
-  if (total < 2) { // no interval
-    HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
-    return SRT_OK;
-  }
-  if (capacity > 0 && (!within_allocation(d_event_rows, (size_t)capacity * SRT_ROW * sizeof(double)) ||
-                       !within_allocation(d_event_meta, (size_t)capacity * 4 * sizeof(int32_t))))
-    return srt_set_error(SRT_EINVAL, "srt_crossings_device: an output has no room for capacity = %lld events", (long long)capacity);
+  if ((rc = event_rows_total("srt_crossings_device", nrays, d_offsets, d_rows, d_count, st, &total)) || total < 2) return rc;
+  if ((rc = event_outputs_fit("srt_crossings_device", capacity, {{d_event_rows, SRT_ROW * sizeof(double)}, {d_event_meta, 4 * sizeof(int32_t)}}))) return rc;
   // Scratch: mask[total] (2 B a row), evoff[total + 1] (8 B a row), the scan's own.  Plain allocations and a wait for the stream
   // before they are freed, as srt_approaches_device below and for its reason: this call comes in pairs (count, then fill), and
   // with hipMallocAsync / hipFreeAsync the second call of a process found recycled blocks -- a tool-mode run of the executable
@@ -362,20 +372,10 @@ extern "C" int srt_approaches_device(int nobs, const srt_observer *observers, in
                               capacity > 0 && (!d_event_rows || !d_event_meta || !d_event_dist), ptrs, 6, scope);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the one thing the host has to know: how many rows there are
   long long total = 0;
-  HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  if (const char *refuse = packed_total_refusal(total, d_rows))
-    return srt_set_error(SRT_EINVAL, "srt_approaches_device: offsets[nrays] = %lld %s", total, refuse);
-  if (total < 2) { // no interval
-    HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int64_t), st));
-    return SRT_OK;
-  }
-  if (capacity > 0 && (!within_allocation(d_event_rows, (size_t)capacity * SRT_ROW * sizeof(double)) ||
-                       !within_allocation(d_event_meta, (size_t)capacity * 4 * sizeof(int32_t)) ||
-                       !within_allocation(d_event_dist, (size_t)capacity * sizeof(double))))
-    return srt_set_error(SRT_EINVAL, "srt_approaches_device: an output has no room for capacity = %lld events", (long long)capacity);
+  if ((rc = event_rows_total("srt_approaches_device", nrays, d_offsets, d_rows, d_count, st, &total)) || total < 2) return rc;
+  if ((rc = event_outputs_fit("srt_approaches_device", capacity, {{d_event_rows, SRT_ROW * sizeof(double)}, {d_event_meta, 4 * sizeof(int32_t)},
+                                                                {d_event_dist, sizeof(double)}}))) return rc;
   // Scratch: the observers, count[total] (4 B a row), evoff[total + 1] (8 B a row), the scan's own.  It is NOT taken from the
   // stream-ordered allocator: with hipMallocAsync / hipFreeAsync here, the second call of a process
   // found recycled blocks and counted no events in 4 of 12 fresh processes on an MI355X (the first call never failed).  Plain
@@ -441,15 +441,13 @@ extern "C" int srt_tubes_device(int64_t nrays, const int64_t *neighbours, const 
                               "an output", nullptr, false, ptrs, 4, scope);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the one thing the host has to know: how many rows there are
   long long total = 0;
-  HIP_OK(hipMemcpyAsync(&total, d_offsets + nrays, sizeof total, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
+  if ((rc = fetch_packed_total(nrays, d_offsets, st, &total))) return rc;
   const char *refuse = packed_total_refusal(total, d_rows);
   // (a single row is a centre row here, where the crossings need two for an interval)
   if (!refuse && total == 1 && !d_rows) refuse = "row, and d_rows is null";
   if (!refuse && total == 1 && !within_allocation(d_rows, (size_t)SRT_ROW * sizeof(double))) refuse = "row, more than the allocation of d_rows holds";
-  if (refuse) return srt_set_error(SRT_EINVAL, "srt_tubes_device: offsets[nrays] = %lld %s", total, refuse);
+  if (refuse) return packed_total_refused("srt_tubes_device", total, refuse);
   if (total == 0) return SRT_OK;
   if ((d_section && !within_allocation(d_section, (size_t)total * 4 * sizeof(double))) ||
       (d_flag && !within_allocation(d_flag, (size_t)total * sizeof(int32_t))))
@@ -553,7 +551,7 @@ extern "C" int srt_bin_rays_device(const srt_bin_params *params, int64_t nrays, 
   }
   (void)hipFreeAsync(d_edges, st); // (also on the error path)
   HIP_OK(e);
-  if (refuse) return srt_set_error(SRT_EINVAL, "srt_bin_rays_device: offsets[nrays] = %lld %s", total, refuse);
+  if (refuse) return packed_total_refused("srt_bin_rays_device", total, refuse);
   return SRT_OK;
 }
 

@@ -1,7 +1,7 @@
 // srt_api_trace.hpp -- the hot path's host side: the checks on srt_params, the launch-cell ray order, a launch's scratch slot,
 // trace_launch (the one launch path of the trace kernels, srt_kernels.hpp) behind the device-buffer entry points, whole and in
 // segments, the queue of running rays, launch timing, the host-buffer entry point srt_trace_batch, and the host iterator over
-// the segments of one launch set (srt_trace_run_*).
+// the segments of one launch set (srt_trace_run_*).  upload_soa3 is the one AoS -> SoA upload of the two host-buffer entry points.
 // A part of srt_api.hip (srt_api_core.hpp).
 #pragma once
 #include "srt_api_core.hpp"
@@ -378,15 +378,9 @@ extern "C" int srt_running_rays_device(int64_t nrays, const int32_t *d_stopcond,
   // ids 0 .. nrays - 1 selected by their flag; DeviceSelect keeps the input's order, so the queue is ascending
   hipcub::CountingInputIterator<int32_t> ids(0);
   auto flags = hipcub::TransformInputIterator<int, IsRunning, const int32_t *>(d_stopcond, IsRunning{});
-  size_t need = 0;
-  HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, need, ids, flags, d_queue, d_count, (int)nrays, st));
-  void *tmp = nullptr;
-  HIP_OK(hipMallocAsync(&tmp, need ? need : 16, st));
-  const hipError_t e = hipcub::DeviceSelect::Flagged(tmp, need, ids, flags, d_queue, d_count, (int)nrays, st);
-  const hipError_t ef = hipFreeAsync(tmp, st); // (also on the error path)
-  HIP_OK(e);
-  HIP_OK(ef);
-  return SRT_OK;
+  return with_cub_temp(st, [&](void *tmp, size_t &bytes) {
+    return hipcub::DeviceSelect::Flagged(tmp, bytes, ids, flags, d_queue, d_count, (int)nrays, st);
+  });
 }
 
 extern "C" int srt_launch_ms(srt_model *m, int back, float *ms) {
@@ -428,6 +422,13 @@ __global__ void aos_to_soa3(const double *in, double *out, long long n) {
     out[2 * n + i] = in[3 * i + 2];
   }
 }
+// a host array [n][3] goes up into `aos` and from there, transposed, into `soa`: a copy and a launch on the null stream, no wait
+// (a caller that reuses `aos` waits before it does)
+static int upload_soa3(const double *h, double *aos, double *soa, int64_t n) {
+  HIP_OK(hipMemcpy(aos, h, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(aos_to_soa3, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const double *)aos, soa, (long long)n);
+  return SRT_OK;
+}
 
 extern "C" int srt_trace_batch(srt_model *m, const srt_params *p, int64_t nrays, const double *pos0,
                                const double *dir0, const double *w0, double *rows, int32_t *nrows,
@@ -453,12 +454,8 @@ extern "C" int srt_trace_batch(srt_model *m, const srt_params *p, int64_t nrays,
       (rc = io_reserve(m, 5, nrow_d * sizeof(double), (void **)&drows)) || (rc = io_reserve(m, 6, (size_t)nrays * sizeof(int32_t), (void **)&d_n)) ||
       (rc = io_reserve(m, 7, (size_t)nrays * sizeof(int32_t), (void **)&d_s)) || (rc = io_reserve(m, 8, 4 * sizeof(int64_t), (void **)&d_c)))
     return rc;
-  HIP_OK(hipMemcpy(a_pos, pos0, v3, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(a_dir, dir0, v3, hipMemcpyHostToDevice));
+  if ((rc = upload_soa3(pos0, a_pos, s_pos, nrays)) || (rc = upload_soa3(dir0, a_dir, s_dir, nrays))) return rc;
   HIP_OK(hipMemcpy(dw, w0, (size_t)nrays * sizeof(double), hipMemcpyHostToDevice));
-  unsigned blocks = (unsigned)((nrays + 255) / 256);
-  hipLaunchKernelGGL(aos_to_soa3, dim3(blocks), dim3(256), 0, 0, (const double *)a_pos, s_pos, (long long)nrays);
-  hipLaunchKernelGGL(aos_to_soa3, dim3(blocks), dim3(256), 0, 0, (const double *)a_dir, s_dir, (long long)nrays);
   (void)hipMemsetAsync(drows, 0, nrow_d * sizeof(double), 0);
   rc = srt_trace_batch_device(m, p, nrays, s_pos, s_dir, dw, drows, d_n, d_s, d_c, nullptr);
   if (rc == SRT_OK) {
@@ -546,12 +543,9 @@ extern "C" int srt_trace_run_open(srt_model *m, const srt_params *p, int64_t nra
       return srt_set_error(SRT_ENOMEM, "segmented trace of %lld rays, %d rows per segment: %s", (long long)nrays, (int)segment_rows,
                            hipGetErrorString(e));
     }
-    const unsigned blocks = (unsigned)((nrays + 255) / 256);
-    HIP_OK(hipMemcpy(aos.p, pos0, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(aos_to_soa3, dim3(blocks), dim3(256), 0, 0, (const double *)aos.p, r->pos.p, (long long)nrays);
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(aos.p, dir0, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(aos_to_soa3, dim3(blocks), dim3(256), 0, 0, (const double *)aos.p, r->dir.p, (long long)nrays);
+    if ((rc = upload_soa3(pos0, aos.p, r->pos.p, nrays))) return rc;
+    HIP_OK(hipDeviceSynchronize()); // (one AoS buffer serves both: the positions are out of it before the directions go in)
+    if ((rc = upload_soa3(dir0, aos.p, r->dir.p, nrays))) return rc;
     HIP_OK(hipMemcpy(r->w.p, w0, n * sizeof(double), hipMemcpyHostToDevice));
     HIP_OK(hipDeviceSynchronize());
   }

@@ -12,48 +12,17 @@ checked to hold the same integers.  A first measurement: it sets no bar.
 
     python tools/bench_binning.py [--repeats 5] [--rays 1000000] [--grid 256] [--out FILE]
 """
-import argparse
-import json
-import os
-import sys
+import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
+import bench_rows_common as common
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--rays", type=int, default=1_000_000)
-    ap.add_argument("--grid", type=int, default=256)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    import torch  # before the library, as in bench.py
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_binning.py needs an MI355X (no CPU fallback)")
-    from stanford_raytracer_amd import api, parallel, workloads as wl
-    from stanford_raytracer_amd.device_batch import DeviceBatch
-
-    api.init(0)
-    dev = torch.device("cuda:0")
-    F, bounds = wl.make_grid(a.grid, half_width=10.0 * wl.R_E)
-    m = api.Model.interp(F, bounds, wl.QS, wl.MS)
-    del F
-    p = api.make_params(fixedstep=0, dt0=1e-3, dtmax=0.1, maxerr=5e-4, tmax=0.5, root=2, minalt=wl.MINALT, maxsteps=256,
-                        outputper=16, del_=1e-6, ray_order=1)
-    pos, d, w = wl.launch_set(a.rays, 3)
-    batch = DeviceBatch(m, p, pos, d, w, dev)
-    o = batch.launch()
-    packed, offsets = parallel.pack_rows_device(o["rows"], o["nrows"], p.outputper)
-    torch.cuda.synchronize()
-    trace_ms = m.last_kernel_ms()
-    n = len(w)
-    total = int(offsets[-1].item())
+    a = common.parser().parse_args()
+    s = common.traced_and_packed(a, "bench_binning.py")
+    torch, api, parallel, wl, dev, st = s.torch, s.api, s.parallel, s.wl, s.dev, s.st
+    packed, offsets, trace_ms, n, total = s.packed, s.offsets, s.trace_ms, s.n, s.total
     roww = torch.rand(max(total, 1), dtype=torch.float64, device=dev)
-    st = torch.cuda.current_stream(dev)
 
     le, lat = np.geomspace(1.0, 10.0, 65), np.deg2rad(np.linspace(-72.0, 72.0, 49))
     half = 10.0 * wl.R_E
@@ -100,12 +69,7 @@ def main():
            "bytes": {"rows_whole": total * 160, "rows_t_pos_vgrel_only": total * 56, "offsets": (n + 1) * 8, "row_weights": total * 8},
            "note": "HIP-event time around parallel.bin_rays_device on the stream: the zeroing of the two maps and the counters, "
                    "srt_bin_rays_device with its 8-byte read of offsets[nrays] and its upload of the edges; a first measurement, no bar"}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    common.emit(res, a.out)
 
 
 if __name__ == "__main__":

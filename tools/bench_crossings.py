@@ -8,61 +8,24 @@ launches; that round trip is inside both figures.  A first measurement: it sets 
 
     python tools/bench_crossings.py [--repeats 5] [--rays 1000000] [--grid 256] [--out FILE]
 """
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import bench_rows_common as common
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--rays", type=int, default=1_000_000)
-    ap.add_argument("--grid", type=int, default=256)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    import torch  # before the library, as in bench.py
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_crossings.py needs an MI355X (no CPU fallback)")
-    from stanford_raytracer_amd import api, parallel, workloads as wl
-    from stanford_raytracer_amd.device_batch import DeviceBatch
-
-    api.init(0)
-    dev = torch.device("cuda:0")
-    F, bounds = wl.make_grid(a.grid, half_width=10.0 * wl.R_E)
-    m = api.Model.interp(F, bounds, wl.QS, wl.MS)
-    del F
-    p = api.make_params(fixedstep=0, dt0=1e-3, dtmax=0.1, maxerr=5e-4, tmax=0.5, root=2, minalt=wl.MINALT, maxsteps=256,
-                        outputper=16, del_=1e-6, ray_order=1)
-    pos, d, w = wl.launch_set(a.rays, 3)
-    batch = DeviceBatch(m, p, pos, d, w, dev)
-    o = batch.launch()
-    packed, offsets = parallel.pack_rows_device(o["rows"], o["nrows"], p.outputper)
-    torch.cuda.synchronize()
-    trace_ms = m.last_kernel_ms()
-    n = len(w)
-    total = int(offsets[-1].item())
-    surf = [api.sphere(1.3 * wl.R_E), api.maglat(0.0), api.maglat(np.deg2rad(20.0)), api.lshell(2.0)]
-    arr, ns = api.surface_array(surf)
-    L = api.lib()
+    a = common.parser().parse_args()
+    s = common.traced_and_packed(a, "bench_crossings.py")
+    torch, api, L, dev, st = s.torch, s.api, s.L, s.dev, s.st
+    packed, offsets, trace_ms, n, total = s.packed, s.offsets, s.trace_ms, s.n, s.total
+    arr, ns = api.surface_array(common.c5_surfaces(s))
     count = torch.zeros(1, dtype=torch.int64, device=dev)
-    st = torch.cuda.current_stream(dev)
 
     def timed(ev, meta, cap):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        api._check(L.srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), ev.data_ptr() if cap else None,
-                                          meta.data_ptr() if cap else None, C.c_int64(cap), count.data_ptr(), st.cuda_stream))
-        e1.record(st)
-        e1.synchronize()
-        return e0.elapsed_time(e1)
+        return common.timed(s, lambda: L.srt_crossings_device(ns, arr, n, offsets.data_ptr(), packed.data_ptr(), ev.data_ptr() if cap else None,
+                                                              meta.data_ptr() if cap else None, C.c_int64(cap), count.data_ptr(), st.cuda_stream))
 
     count_ms = [timed(None, None, 0) for _ in range(a.repeats + 1)][1:]
     nev = int(count.item())
@@ -87,12 +50,7 @@ def main():
            "note": "HIP-event time around srt_crossings_device on the stream, including its 8-byte read of offsets[nrays]; "
                    "a first measurement, no bar"}
     res["count_only_GBs_of_whole_rows"] = round(total * 160 / (res["count_only_ms_median"] * 1e-3) / 1e9, 1)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    common.emit(res, a.out)
 
 
 if __name__ == "__main__":

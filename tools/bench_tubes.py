@@ -8,61 +8,25 @@ surfaces of bench_crossings.py.  A first measurement: it sets no bar.
 
     python tools/bench_tubes.py [--repeats 5] [--rays 1000000] [--grid 256] [--out FILE]
 """
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import numpy as np
 
-import numpy as np  # noqa: E402
+import bench_rows_common as common
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--rays", type=int, default=1_000_000)
-    ap.add_argument("--grid", type=int, default=256)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    import torch  # before the library, as in bench.py
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_tubes.py needs an MI355X (no CPU fallback)")
-    from stanford_raytracer_amd import api, parallel, workloads as wl
-    from stanford_raytracer_amd.device_batch import DeviceBatch
-
-    api.init(0)
-    dev = torch.device("cuda:0")
-    F, bounds = wl.make_grid(a.grid, half_width=10.0 * wl.R_E)
-    m = api.Model.interp(F, bounds, wl.QS, wl.MS)
-    del F
-    p = api.make_params(fixedstep=0, dt0=1e-3, dtmax=0.1, maxerr=5e-4, tmax=0.5, root=2, minalt=wl.MINALT, maxsteps=256,
-                        outputper=16, del_=1e-6, ray_order=1)
-    pos, d, w = wl.launch_set(a.rays, 3)
-    batch = DeviceBatch(m, p, pos, d, w, dev)
-    o = batch.launch()
-    packed, offsets = parallel.pack_rows_device(o["rows"], o["nrows"], p.outputper)
-    torch.cuda.synchronize()
-    trace_ms = m.last_kernel_ms()
-    n = len(w)
-    total = int(offsets[-1].item())
-    L = api.lib()
+    a = common.parser().parse_args()
+    s = common.traced_and_packed(a, "bench_tubes.py")
+    torch, api, L, dev, st = s.torch, s.api, s.L, s.dev, s.st
+    packed, offsets, trace_ms, n, total = s.packed, s.offsets, s.trace_ms, s.n, s.total
     count = torch.zeros(1, dtype=torch.int64, device=dev)
-    st = torch.cuda.current_stream(dev)
 
     def timed(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        api._check(call())
-        e1.record(st)
-        e1.synchronize()
-        return e0.elapsed_time(e1)
+        return common.timed(s, call)
 
     # the crossings' count pass on the same rows, in the same run
-    surf, ns = api.surface_array([api.sphere(1.3 * wl.R_E), api.maglat(0.0), api.maglat(np.deg2rad(20.0)), api.lshell(2.0)])
+    surf, ns = api.surface_array(common.c5_surfaces(s))
     cx_ms = [timed(lambda: L.srt_crossings_device(ns, surf, n, offsets.data_ptr(), packed.data_ptr(), None, None, C.c_int64(0),
                                                   count.data_ptr(), st.cuda_stream)) for _ in range(a.repeats + 1)][1:]
     nb = np.full((n, 2), -1, dtype=np.int64)
@@ -90,12 +54,7 @@ def main():
            "crossings_count_only_ms_median": round(float(np.median(cx_ms)), 4), "crossings_count_only_ms": [round(v, 4) for v in cx_ms],
            "note": "HIP-event time around srt_tubes_device on the stream, including its copy of the neighbours and its 8-byte read "
                    "of offsets[nrays]; a first measurement, no bar"}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    common.emit(res, a.out)
 
 
 if __name__ == "__main__":
