@@ -4,6 +4,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <thread>
 
 #include "srt_host.hpp"
@@ -258,28 +259,42 @@ bool read_newray(const char *path, NgoConfig &c, std::string &err) {
   return true;
 }
 
+static const char NSPEC_REFUSED[] = "nspec must be 1..4 (SRT_MAXSPEC: this library carries at most four species; see INTEGRATION.md section 1)";
+// the shape a grid header announces, refused in the words of every grid reader
+static bool grid_shape_ok(const GridFile &g, std::string &err) {
+  if (g.nspec < 1 || g.nspec > 4) { err = NSPEC_REFUSED; return false; }
+  if (g.nx < 2 || g.ny < 2 || g.nz < 2) { err = "grid needs >= 2 nodes per axis"; return false; }
+  return true;
+}
+
 // --- the record-by-record reader (exactly the Fortran's READ semantics; slow: one strtod at a time)
 static bool read_grid_file_records(const char *path, GridFile &g, std::string &err) {
   ListReader r(path);
-  if (!r.ok()) { err = "cannot open"; return false; }
+  struct stat st;
+  if (!r.ok() || stat(path, &st) != 0) { err = "cannot open"; return false; }
   double v[8];
   if (r.read(5, v) != 5) { err = "size header incomplete"; return false; }
   g.compder = (int)v[0]; g.nspec = (int)v[1]; g.nx = (int)v[2]; g.ny = (int)v[3]; g.nz = (int)v[4];
-  if (g.nspec < 1 || g.nspec > 4) { err = "nspec must be 1..4 (SRT_MAXSPEC: this library carries at most four species; see INTEGRATION.md section 1)"; return false; }
-  if (g.nx < 2 || g.ny < 2 || g.nz < 2) { err = "grid needs >= 2 nodes per axis"; return false; }
+  if (!grid_shape_ok(g, err)) return false;
   if (r.read(6, g.bounds) != 6) { err = "bounds incomplete"; return false; }
   if (r.read(g.nspec, g.qs) != g.nspec) { err = "charges incomplete"; return false; }
   if (r.read(g.nspec, g.ms) != g.nspec) { err = "masses incomplete"; return false; }
+  // a value takes two bytes of text at the least (a digit and its separator): a header that announces more values than the
+  // file has room for is refused before anything of that size is allocated (in double: three int axes cannot overflow it)
+  const double announced = (double)g.nx * g.ny * g.nz * g.nspec, room = (double)st.st_size / 2.0;
+  if (announced > room) { err = "grid values truncated"; return false; }
   size_t nnode = (size_t)g.nx * g.ny * g.nz, n = nnode * g.nspec;
   g.F.resize(n);
   for (size_t c = 0; c < nnode; ++c) // one record per node (:100-106)
     if (r.read(g.nspec, g.F.data() + c * g.nspec) != g.nspec) { err = "grid values truncated"; return false; }
   g.have_derivs = (g.compder == 1);
-  if (g.have_derivs)
+  if (g.have_derivs) {
+    if (8.0 * announced > room) { err = "derivative block truncated"; return false; }
     for (int a = 0; a < 7; ++a) {
       g.derivs[a].resize(n);
       if (r.read((int64_t)n, g.derivs[a].data()) != (int64_t)n) { err = "derivative block truncated"; return false; }
     }
+  }
   return true;
 }
 
@@ -324,6 +339,52 @@ struct MappedFile {
     if (fd >= 0) close(fd);
   }
 };
+// every numeric token of [b, e), parsed by all host cores: the pieces hold them in order; false on a non-numeric token
+bool parse_numbers(const char *b, const char *e, std::vector<std::vector<double>> &part) {
+  unsigned nt = std::thread::hardware_concurrency();
+  nt = nt ? (nt > 32 ? 32 : nt) : 1;
+  if ((size_t)(e - b) < (size_t)nt * 4096) nt = 1;
+  std::vector<const char *> cut(nt + 1); // cut at record boundaries, one piece per thread
+  cut[0] = b;
+  cut[nt] = e;
+  for (unsigned t = 1; t < nt; ++t) {
+    const char *c = b + (size_t)(e - b) * t / nt;
+    const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
+    cut[t] = nl ? nl + 1 : e;
+  }
+  part.assign(nt, std::vector<double>());
+  std::vector<char> good(nt, 1);
+  std::vector<std::thread> th;
+  for (unsigned t = 0; t < nt; ++t)
+    th.emplace_back([&, t] {
+      part[t].reserve((size_t)(cut[t + 1] - cut[t]) / 16 + 16);
+      good[t] = parse_tokens(cut[t], cut[t + 1], part[t]) ? 1 : 0;
+    });
+  for (auto &x : th) x.join();
+  for (unsigned t = 0; t < nt; ++t)
+    if (!good[t]) return false;
+  return true;
+}
+size_t count_numbers(const std::vector<std::vector<double>> &part) {
+  size_t total = 0;
+  for (const auto &p : part) total += p.size();
+  return total;
+}
+// a binary side-format is known by the eight bytes it starts with
+bool has_magic(const char *path, const char magic[8]) {
+  FILE *f = fopen(path, "rb");
+  if (!f) return false;
+  char m[8];
+  const bool ok = fread(m, 1, 8, f) == 8 && memcmp(m, magic, 8) == 0;
+  fclose(f);
+  return ok;
+}
+// a malloc'd array of n values for the caller (srt_free), a copy of src[n] where src is given; null: out of memory
+template <class T> T *copy_out(size_t n, const T *src = nullptr) {
+  T *p = (T *)malloc(sizeof(T) * (n ? n : 1));
+  if (p && src && n) memcpy(p, src, sizeof(T) * n);
+  return p;
+}
 const char GRID_MAGIC[8] = {'S', 'R', 'T', 'G', 'R', 'I', 'D', '1'};
 struct GridBinHeader { // 8 + 5*4 + 4 (pad) + 14*8 = 144 bytes, then F, then 7 derivative blocks if compder == 1
   char magic[8];
@@ -332,15 +393,6 @@ struct GridBinHeader { // 8 + 5*4 + 4 (pad) + 14*8 = 144 bytes, then F, then 7 d
 };
 } // namespace
 
-bool is_binary_grid(const char *path) {
-  FILE *f = fopen(path, "rb");
-  if (!f) return false;
-  char m[8] = {0};
-  size_t k = fread(m, 1, 8, f);
-  fclose(f);
-  return k == 8 && memcmp(m, GRID_MAGIC, 8) == 0;
-}
-
 static bool read_grid_binary(const char *path, GridFile &g, std::string &err) {
   MappedFile mf(path);
   if (!mf.p) { err = "cannot open"; return false; }
@@ -348,8 +400,7 @@ static bool read_grid_binary(const char *path, GridFile &g, std::string &err) {
   GridBinHeader h;
   memcpy(&h, mf.p, sizeof h);
   g.compder = h.compder; g.nspec = h.nspec; g.nx = h.nx; g.ny = h.ny; g.nz = h.nz;
-  if (g.nspec < 1 || g.nspec > 4) { err = "nspec must be 1..4 (SRT_MAXSPEC: this library carries at most four species; see INTEGRATION.md section 1)"; return false; }
-  if (g.nx < 2 || g.ny < 2 || g.nz < 2) { err = "grid needs >= 2 nodes per axis"; return false; }
+  if (!grid_shape_ok(g, err)) return false;
   memcpy(g.bounds, h.bounds, sizeof g.bounds);
   memcpy(g.qs, h.qs, sizeof g.qs);
   memcpy(g.ms, h.ms, sizeof g.ms);
@@ -368,7 +419,9 @@ static bool read_grid_binary(const char *path, GridFile &g, std::string &err) {
   return true;
 }
 
-bool write_grid_binary(const char *path, const GridFile &g, std::string &err) {
+// binary side-format: the 144-byte header followed by the value blocks of the text format as raw little-endian doubles in
+// the same order
+static bool write_grid_binary(const char *path, const GridFile &g, std::string &err) {
   FILE *f = fopen(path, "wb");
   if (!f) { err = "cannot open for writing"; return false; }
   GridBinHeader h;
@@ -388,43 +441,19 @@ bool write_grid_binary(const char *path, const GridFile &g, std::string &err) {
 
 // every numeric token of a text file, in order, parsed by all host cores; false if the file cannot be opened or holds
 // a non-numeric token
-bool read_all_numbers(const char *path, std::vector<double> &all, std::string &err) {
+static bool read_all_numbers(const char *path, std::vector<double> &all, std::string &err) {
   MappedFile mf(path);
   if (!mf.p) { err = "cannot open"; return false; }
-  const char *b = mf.p, *e = mf.p + mf.n;
-  unsigned nt = std::thread::hardware_concurrency();
-  nt = nt ? (nt > 32 ? 32 : nt) : 1;
-  if ((size_t)(e - b) < (size_t)nt * 4096) nt = 1;
-  std::vector<const char *> cut(nt + 1);
-  cut[0] = b;
-  cut[nt] = e;
-  for (unsigned t = 1; t < nt; ++t) {
-    const char *c = b + (size_t)(e - b) * t / nt;
-    const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
-    cut[t] = nl ? nl + 1 : e;
-  }
-  std::vector<std::vector<double>> part(nt);
-  std::vector<char> good(nt, 1);
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; ++t)
-    th.emplace_back([&, t] {
-      part[t].reserve((size_t)(cut[t + 1] - cut[t]) / 16 + 16);
-      good[t] = parse_tokens(cut[t], cut[t + 1], part[t]) ? 1 : 0;
-    });
-  for (auto &x : th) x.join();
-  size_t total = 0;
-  for (unsigned t = 0; t < nt; ++t) {
-    if (!good[t]) { err = "non-numeric token"; return false; }
-    total += part[t].size();
-  }
+  std::vector<std::vector<double>> part;
+  if (!parse_numbers(mf.p, mf.p + mf.n, part)) { err = "non-numeric token"; return false; }
   all.clear();
-  all.reserve(total);
-  for (unsigned t = 0; t < nt; ++t) all.insert(all.end(), part[t].begin(), part[t].end());
+  all.reserve(count_numbers(part));
+  for (const auto &p : part) all.insert(all.end(), p.begin(), p.end());
   return true;
 }
 
 bool read_grid_file(const char *path, GridFile &g, std::string &err) {
-  if (is_binary_grid(path)) return read_grid_binary(path, g, err);
+  if (has_magic(path, GRID_MAGIC)) return read_grid_binary(path, g, err);
   MappedFile mf(path);
   if (!mf.p) { err = "cannot open"; return false; }
   // header: the first four records (sizes; bounds; charges; masses)
@@ -445,8 +474,7 @@ bool read_grid_file(const char *path, GridFile &g, std::string &err) {
   };
   if (!record(5)) { err = "size header incomplete"; return false; }
   g.compder = (int)hv[0]; g.nspec = (int)hv[1]; g.nx = (int)hv[2]; g.ny = (int)hv[3]; g.nz = (int)hv[4];
-  if (g.nspec < 1 || g.nspec > 4) { err = "nspec must be 1..4 (SRT_MAXSPEC: this library carries at most four species; see INTEGRATION.md section 1)"; return false; }
-  if (g.nx < 2 || g.ny < 2 || g.nz < 2) { err = "grid needs >= 2 nodes per axis"; return false; }
+  if (!grid_shape_ok(g, err)) return false;
   if (!record(6)) { err = "bounds incomplete"; return false; }
   if (!record(g.nspec)) { err = "charges incomplete"; return false; }
   if (!record(g.nspec)) { err = "masses incomplete"; return false; }
@@ -454,32 +482,9 @@ bool read_grid_file(const char *path, GridFile &g, std::string &err) {
   for (int k = 0; k < g.nspec; ++k) { g.qs[k] = hv[11 + k]; g.ms[k] = hv[11 + g.nspec + k]; }
   const size_t nnode = (size_t)g.nx * g.ny * g.nz, n = nnode * g.nspec;
   g.have_derivs = (g.compder == 1);
-  const size_t want = n * (g.have_derivs ? 8 : 1);
-  // value block: cut at record boundaries, one piece per thread
-  unsigned nt = std::thread::hardware_concurrency();
-  nt = nt ? (nt > 32 ? 32 : nt) : 1;
-  if ((size_t)(e - b) < (size_t)nt * 4096) nt = 1;
-  std::vector<const char *> cut(nt + 1);
-  cut[0] = b;
-  cut[nt] = e;
-  for (unsigned t = 1; t < nt; ++t) {
-    const char *c = b + (size_t)(e - b) * t / nt;
-    const char *nl = (const char *)memchr(c, '\n', (size_t)(e - c));
-    cut[t] = nl ? nl + 1 : e;
-  }
-  std::vector<std::vector<double>> part(nt);
-  std::vector<char> good(nt, 1);
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < nt; ++t)
-    th.emplace_back([&, t] {
-      part[t].reserve((size_t)(cut[t + 1] - cut[t]) / 20 + 16);
-      good[t] = parse_tokens(cut[t], cut[t + 1], part[t]) ? 1 : 0;
-    });
-  for (auto &x : th) x.join();
-  size_t total = 0;
-  bool allgood = true;
-  for (unsigned t = 0; t < nt; ++t) { total += part[t].size(); allgood = allgood && good[t]; }
-  if (!allgood || total != want) {
+  // the value block; the count is compared in double, which the product of three int axes cannot overflow
+  std::vector<std::vector<double>> part;
+  if (!parse_numbers(b, e, part) || (double)count_numbers(part) != (double)g.nx * g.ny * g.nz * g.nspec * (g.have_derivs ? 8 : 1)) {
     // not the plain one-record-per-node layout (extra fields on a line, a stray token, ...): re-read with the
     // Fortran's record semantics
     g = GridFile();
@@ -488,41 +493,235 @@ bool read_grid_file(const char *path, GridFile &g, std::string &err) {
   g.F.resize(n);
   if (g.have_derivs)
     for (int a = 0; a < 7; ++a) g.derivs[a].resize(n);
-  size_t pos = 0;
-  for (unsigned t = 0; t < nt; ++t) {
-    for (double v : part[t]) {
-      size_t blk = pos / n, off = pos % n;
-      (blk == 0 ? g.F : g.derivs[blk - 1])[off] = v;
-      ++pos;
+  size_t pos = 0; // the pieces, end to end, are F and then the seven derivative blocks
+  for (auto &p : part) {
+    for (size_t i = 0; i < p.size();) {
+      const size_t blk = pos / n, off = pos % n, m = std::min(p.size() - i, n - off);
+      memcpy((blk == 0 ? g.F : g.derivs[blk - 1]).data() + off, p.data() + i, m * sizeof(double));
+      i += m;
+      pos += m;
     }
-    std::vector<double>().swap(part[t]);
+    std::vector<double>().swap(p);
   }
   return true;
 }
 
 // ---------------------------------------------------------------------------------------------
-void format_es24(double v, char out[25]) {
-  char tmp[64];
-  if (std::isnan(v)) {
-    snprintf(out, 25, "%24s", "NaN");
+// the es24.15e3 edit descriptor into exactly 24 characters (no terminator), the exponent widened to three digits by hand;
+// NaN, Inf and -Inf right-aligned as the Fortran writes them
+static void put_es24(double v, char *out) {
+  char tmp[40];
+  if (!std::isfinite(v)) {
+    const char *s = std::isnan(v) ? "NaN" : v > 0 ? "Inf" : "-Inf";
+    const size_t n = strlen(s);
+    memset(out, ' ', 24 - n);
+    memcpy(out + 24 - n, s, n);
     return;
   }
-  if (std::isinf(v)) {
-    snprintf(out, 25, "%24s", v > 0 ? "Inf" : "-Inf");
-    return;
+  // [-]d.ddddddddddddddde+XX[X]: std::to_chars with a precision is correctly rounded like printf's %.15E (and 5x faster)
+  const std::to_chars_result tr = std::to_chars(tmp, tmp + sizeof tmp - 1, v, std::chars_format::scientific, 15);
+  const int n = (int)(tr.ptr - tmp);
+  tmp[n] = 0;
+  const char *e = (const char *)memchr(tmp, 'e', (size_t)n);
+  const int mant = (int)(e - tmp);
+  int ex = atoi(e + 2);
+  const int len = mant + 5;
+  char *q = out;
+  for (int k = len; k < 24; ++k) *q++ = ' ';
+  memcpy(q, tmp, (size_t)mant);
+  q += mant;
+  *q++ = 'E';
+  *q++ = e[1];
+  *q++ = (char)('0' + (ex / 100) % 10);
+  *q++ = (char)('0' + (ex / 10) % 10);
+  *q++ = (char)('0' + ex % 10);
+}
+
+// A text file of Fortran-formatted records being written.  It owns the FILE and its 4 MB buffer; a record is put together
+// field by field and goes out at end(); what went wrong, at the opening or at any write, is said once, by close().
+namespace {
+class TextWriter {
+public:
+  explicit TextWriter(const char *path) : path_(path), f_(fopen(path, "w")), buf_(f_ ? (size_t)1 << 22 : 0) {
+    if (f_) setvbuf(f_, buf_.data(), _IOFBF, buf_.size());
   }
-  snprintf(tmp, sizeof tmp, "%.15E", v); // d.dddddddddddddddE+XX
-  char *e = strchr(tmp, 'E');
-  int ex = atoi(e + 1);
-  *e = 0;
-  char buf[64];
-  snprintf(buf, sizeof buf, "%sE%c%03d", tmp, ex < 0 ? '-' : '+', ex < 0 ? -ex : ex);
-  snprintf(out, 25, "%24s", buf);
+  ~TextWriter() {
+    if (f_) fclose(f_);
+  }
+  TextWriter(const TextWriter &) = delete;
+  TextWriter &operator=(const TextWriter &) = delete;
+  bool ok() const { return f_ != nullptr; }
+  TextWriter &i10(long long v) { return integer("%10lld", v); }
+  TextWriter &i20(long long v) { return integer("%20lld", v); }
+  TextWriter &es24(double v) {
+    rec_.resize(rec_.size() + 24);
+    put_es24(v, &rec_[rec_.size() - 24]);
+    return *this;
+  }
+  TextWriter &es24(const double *v, size_t n) {
+    for (size_t k = 0; k < n; ++k) es24(v[k]);
+    return *this;
+  }
+  void end() {
+    rec_ += '\n';
+    if (f_) fwrite(rec_.data(), 1, rec_.size(), f_);
+    rec_.clear();
+  }
+  int close() { // SRT_OK, or SRT_EIO and its text
+    if (!f_) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path_);
+    const bool failed = ferror(f_) != 0;
+    const bool closed = fclose(f_) == 0;
+    f_ = nullptr;
+    return failed || !closed ? srt_set_error(SRT_EIO, "%s: write failed", path_) : SRT_OK;
+  }
+
+private:
+  TextWriter &integer(const char *fmt, long long v) {
+    char b[24];
+    rec_.append(b, (size_t)snprintf(b, sizeof b, fmt, v));
+    return *this;
+  }
+  const char *path_;
+  FILE *f_;
+  std::vector<char> buf_;
+  std::string rec_;
+};
+// one text file: opened, written by body(TextWriter &) if it could be opened, closed -> SRT_OK, or SRT_EIO and its text
+template <class Body> int write_text(const char *path, Body body) {
+  TextWriter t(path);
+  if (t.ok()) body(t);
+  return t.close();
+}
+
+// an i10 field holds a ray number of at most ten digits: beyond, Fortran prints asterisks, and a fixed-length record could not
+// hold the number -- every writer refuses rather than shifts or truncates
+bool fits_i10(long long first, long long last) { return first >= 0 && last <= 9999999999ll; }
+int refuse_beyond_i10(const char *who, const char *what, int64_t n, const int64_t *raynum) {
+  for (int64_t k = 0; k < n; ++k)
+    if (!fits_i10(raynum[k], raynum[k]))
+      return srt_set_error(SRT_EINVAL, "%s: ray number %lld of %s %lld does not fit the record's i10 field", who, (long long)raynum[k], what,
+                           (long long)k);
+  return SRT_OK;
+}
+// the offsets of a packed row set start at 0 and do not decrease; `who` is "" or the caller's name and ": "
+int refuse_bad_offsets(const char *who, int64_t nrays, const int64_t *offsets) {
+  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "%soffsets[0] = %lld: the first ray's rows start at 0", who, (long long)offsets[0]);
+  for (int64_t r = 0; r < nrays; ++r)
+    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "%soffsets decrease at ray %lld", who, (long long)r);
+  return SRT_OK;
+}
+} // namespace
+
+// ---- model-4 sample files: the reference builder's text (gcpm_dens_model_buildgrid_random.f95:196-208 for the
+// header, helpermod :37-43 for one sample per record, es24.15e3) and the binary side-format "SRTPTS01": int32 nspec, int32 0,
+// int64 npts, bounds[6], qs[4], ms[4] (a 136-byte header), then npts records of 3 + nspec little-endian doubles ----
+namespace {
+const char PTS_MAGIC[8] = {'S', 'R', 'T', 'P', 'T', 'S', '0', '1'};
+struct PtsHeader {
+  char magic[8];
+  int32_t nspec, zero;
+  int64_t npts;
+  double bounds[6], qs[4], ms[4];
+};
+// a text sample file taken as one run of numbers -- nspec, 6 bounds, nspec charges, nspec masses, then 3 + nspec per sample --
+// which it is when every record holds exactly what its READ takes
+struct PointsText {
+  int nspec = 0;
+  int64_t npts = 0;
+  const double *bounds = nullptr, *qs = nullptr, *ms = nullptr, *rec = nullptr;
+};
+bool split_points_text(const std::vector<double> &all, PointsText &p) {
+  if (all.size() < 7) return false;
+  p.nspec = (int)all[0];
+  if (p.nspec < 1 || p.nspec > 4 || all.size() < (size_t)(7 + 2 * p.nspec) || (all.size() - 7 - 2 * p.nspec) % (size_t)(3 + p.nspec) != 0)
+    return false;
+  p.npts = (int64_t)((all.size() - 7 - 2 * p.nspec) / (size_t)(3 + p.nspec));
+  p.bounds = &all[1];
+  p.qs = &all[7];
+  p.ms = p.qs + p.nspec;
+  p.rec = p.ms + p.nspec;
+  return true;
+}
+bool read_points_binary(const char *path, int &nspec, double qs[4], double ms[4], std::vector<double> &rec, std::string &err) {
+  MappedFile mf(path);
+  if (!mf.p) { err = "cannot open"; return false; }
+  err = "truncated or malformed binary sample file";
+  PtsHeader h;
+  if (mf.n < sizeof h) return false;
+  memcpy(&h, mf.p, sizeof h);
+  if (memcmp(h.magic, PTS_MAGIC, 8) != 0 || h.nspec < 1 || h.nspec > 4 || h.npts < 0) return false;
+  // the records the file has room for against the count its header announces: a division, which cannot overflow
+  const size_t w = (size_t)(3 + h.nspec);
+  if ((mf.n - sizeof h) / (w * sizeof(double)) < (uint64_t)h.npts) return false;
+  nspec = h.nspec;
+  for (int k = 0; k < nspec; ++k) { qs[k] = h.qs[k]; ms[k] = h.ms[k]; }
+  rec.resize((size_t)h.npts * w);
+  if (!rec.empty()) memcpy(rec.data(), mf.p + sizeof h, rec.size() * sizeof(double));
+  err.clear();
+  return true;
+}
+int write_points_file(const char *path, bool binary, int nspec, int64_t npts, const double bounds[6], const double *qs, const double *ms,
+                      const double *rec) {
+  const size_t w = (size_t)(3 + nspec);
+  if (binary) {
+    FILE *f = fopen(path, "wb");
+    if (!f) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
+    PtsHeader h;
+    memset(&h, 0, sizeof h);
+    memcpy(h.magic, PTS_MAGIC, 8);
+    h.nspec = nspec;
+    h.npts = npts;
+    for (int k = 0; k < 6; ++k) h.bounds[k] = bounds[k];
+    for (int k = 0; k < nspec; ++k) { h.qs[k] = qs[k]; h.ms[k] = ms[k]; }
+    bool ok = fwrite(&h, sizeof h, 1, f) == 1 && fwrite(rec, sizeof(double), (size_t)npts * w, f) == (size_t)npts * w;
+    ok = (fclose(f) == 0) && ok;
+    return ok ? SRT_OK : srt_set_error(SRT_EIO, "%s: write failed", path);
+  }
+  return write_text(path, [&](TextWriter &t) {
+    t.i10(nspec).end();
+    t.es24(bounds, 6).end();
+    t.es24(qs, (size_t)nspec).end();
+    t.es24(ms, (size_t)nspec).end();
+    for (int64_t i = 0; i < npts; ++i) t.es24(rec + (size_t)i * w, w).end();
+  });
+}
+} // namespace
+
+bool read_points_file(const char *path, int &nspec, double qs[4], double ms[4], std::vector<double> &rec, std::string &err) {
+  if (has_magic(path, PTS_MAGIC)) return read_points_binary(path, nspec, qs, ms, rec, err);
+  // fast path: the whole file tokenised by all cores
+  std::vector<double> all;
+  std::string unused;
+  PointsText p;
+  if (read_all_numbers(path, all, unused) && split_points_text(all, p)) {
+    nspec = p.nspec;
+    for (int k = 0; k < nspec; ++k) { qs[k] = p.qs[k]; ms[k] = p.ms[k]; }
+    rec.assign(p.rec, p.rec + (size_t)p.npts * (size_t)(3 + nspec));
+    return true;
+  }
+  // the Fortran's record semantics, one READ at a time
+  ListReader r(path);
+  if (!r.ok()) {
+    err = "cannot open";
+    return false;
+  }
+  double hdr[7];
+  if (r.read(7, hdr) != 7) { err = "header (nspec + bounds) incomplete"; return false; }
+  nspec = (int)hdr[0];
+  if (nspec < 1 || nspec > 4) { err = NSPEC_REFUSED; return false; }
+  if (r.read(nspec, qs) != nspec || r.read(nspec, ms) != nspec) { err = "charges/masses incomplete"; return false; }
+  double row[8];
+  while (r.read(3 + nspec, row) == 3 + nspec) rec.insert(rec.end(), row, row + 3 + nspec);
+  return true;
 }
 
 } // namespace srt_host
 
 // ================================================================================ C ABI (file I/O)
+using srt_host::copy_out;
+using srt_host::put_es24;
+using srt_host::TextWriter;
+
 extern "C" void srt_free(void *p) { free(p); }
 
 // ---- model-3 grid files: text of gcpm_dens_model_buildgrid.f95:302-327 <-> binary side-format
@@ -537,13 +736,12 @@ extern "C" int srt_grid_file_read(const char *path, int32_t dims[5], double boun
   memcpy(qs, g.qs, 4 * sizeof(double));
   memcpy(ms, g.ms, 4 * sizeof(double));
   const size_t n = g.F.size();
-  *F = (double *)malloc(n * sizeof(double));
+  *F = copy_out(n, g.F.data());
   if (!*F) return srt_set_error(SRT_ENOMEM, "grid of %zu values", n);
-  memcpy(*F, g.F.data(), n * sizeof(double));
   if (derivs) {
     *derivs = nullptr;
     if (g.have_derivs) {
-      *derivs = (double *)malloc(7 * n * sizeof(double));
+      *derivs = copy_out<double>(7 * n);
       if (!*derivs) return srt_set_error(SRT_ENOMEM, "derivative blocks of %zu values", 7 * n);
       for (int a = 0; a < 7; ++a) memcpy(*derivs + (size_t)a * n, g.derivs[a].data(), n * sizeof(double));
     }
@@ -573,28 +771,14 @@ extern "C" int srt_grid_file_write(const char *path, int binary, int nspec, int 
   // text, byte for byte what gcpm_dens_model_buildgrid.f95:302-327 writes: (5i10); (6es24.15e3); charges; masses;
   // then every value on its own record in es24.15e3 (16 significant digits -- the format's, not ours: use the
   // binary form where the last bit matters)
-  FILE *f = fopen(path, "w");
-  if (!f) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
-  std::vector<char> big(1 << 22);
-  setvbuf(f, big.data(), _IOFBF, big.size());
-  char num[25];
-  fprintf(f, "%10d%10d%10d%10d%10d\n", derivs ? 1 : 0, nspec, nx, ny, nz);
-  for (int k = 0; k < 6; ++k) { srt_host::format_es24(bounds[k], num); fputs(num, f); }
-  fputc('\n', f);
-  for (int k = 0; k < nspec; ++k) { srt_host::format_es24(qs[k], num); fputs(num, f); }
-  fputc('\n', f);
-  for (int k = 0; k < nspec; ++k) { srt_host::format_es24(ms[k], num); fputs(num, f); }
-  fputc('\n', f);
-  for (int blk = 0; blk < (derivs ? 8 : 1); ++blk) {
-    const double *v = blk == 0 ? F : derivs + (size_t)(blk - 1) * n;
-    for (size_t c = 0; c < n; ++c) {
-      srt_host::format_es24(v[c], num);
-      num[24] = '\n';
-      fwrite(num, 1, 25, f);
-    }
-  }
-  if (fclose(f) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
-  return SRT_OK;
+  return srt_host::write_text(path, [&](TextWriter &t) {
+    t.i10(derivs ? 1 : 0).i10(nspec).i10(nx).i10(ny).i10(nz).end();
+    t.es24(bounds, 6).end();
+    t.es24(qs, (size_t)nspec).end();
+    t.es24(ms, (size_t)nspec).end();
+    for (size_t c = 0; c < n; ++c) t.es24(F[c]).end();
+    for (size_t c = 0; derivs && c < 7 * n; ++c) t.es24(derivs[c]).end();
+  });
 }
 
 extern "C" int srt_grid_file_convert(const char *in, const char *out_binary) {
@@ -606,7 +790,7 @@ extern "C" int srt_grid_file_convert(const char *in, const char *out_binary) {
   return SRT_OK;
 }
 
-extern "C" int srt_grid_file_is_binary(const char *path) { return path && srt_host::is_binary_grid(path) ? 1 : 0; }
+extern "C" int srt_grid_file_is_binary(const char *path) { return path && srt_host::has_magic(path, srt_host::GRID_MAGIC) ? 1 : 0; }
 
 extern "C" int64_t srt_read_rays_file(const char *path, double **pos0, double **dir0, double **w0) {
   if (!path || !pos0 || !dir0 || !w0) return srt_set_error(SRT_EINVAL, "null argument");
@@ -616,9 +800,14 @@ extern "C" int64_t srt_read_rays_file(const char *path, double **pos0, double **
   double v[7];
   while (r.read(7, v) == 7) all.insert(all.end(), v, v + 7); // read(infile,*) pos0, dir0, w ; EOF ends (driver:1146)
   int64_t n = (int64_t)(all.size() / 7);
-  *pos0 = (double *)malloc(sizeof(double) * 3 * (n ? n : 1));
-  *dir0 = (double *)malloc(sizeof(double) * 3 * (n ? n : 1));
-  *w0 = (double *)malloc(sizeof(double) * (n ? n : 1));
+  *pos0 = copy_out<double>(3 * (size_t)n);
+  *dir0 = copy_out<double>(3 * (size_t)n);
+  *w0 = copy_out<double>((size_t)n);
+  if (!*pos0 || !*dir0 || !*w0) {
+    free(*pos0), free(*dir0), free(*w0);
+    *pos0 = *dir0 = *w0 = nullptr;
+    return srt_set_error(SRT_ENOMEM, "%s: %lld rays", path, (long long)n);
+  }
   for (int64_t i = 0; i < n; ++i) {
     for (int c = 0; c < 3; ++c) {
       (*pos0)[3 * i + c] = all[7 * i + c];
@@ -659,12 +848,11 @@ extern "C" int64_t srt_read_ray_file(const char *path, int32_t *nspec_out, doubl
       if (r == 0 || v[0] != all[(size_t)(r - 1) * per] || v[2] == 0.0) ++nray; // (a ray's first record is its row 0: t = 0)
     }
   }
-  const int64_t na = nray ? nray : 1, nr = nrec ? nrec : 1;
-  *raynum = (int64_t *)malloc(sizeof(int64_t) * na);
-  *stopcond = (int32_t *)malloc(sizeof(int32_t) * na);
-  *kept = (int32_t *)malloc(sizeof(int32_t) * na);
-  *w0 = (double *)malloc(sizeof(double) * na);
-  *rows = (double *)malloc(sizeof(double) * SRT_ROW * nr);
+  *raynum = copy_out<int64_t>((size_t)nray);
+  *stopcond = copy_out<int32_t>((size_t)nray);
+  *kept = copy_out<int32_t>((size_t)nray);
+  *w0 = copy_out<double>((size_t)nray);
+  *rows = copy_out<double>((size_t)SRT_ROW * (size_t)nrec);
   if (!*raynum || !*stopcond || !*kept || !*w0 || !*rows) {
     free(*raynum), free(*stopcond), free(*kept), free(*w0), free(*rows);
     *raynum = nullptr, *stopcond = nullptr, *kept = nullptr, *w0 = nullptr, *rows = nullptr;
@@ -700,34 +888,6 @@ extern "C" int64_t srt_read_ray_file(const char *path, int32_t *nspec_out, doubl
 // record format of raytracer_driver.f95:1197-1217:
 //   (i10, i10, 17es24.15e3, i10) raynum, stopcond, t, pos, vprel, vgrel, n, B0, w, nspec
 //   then nspec x es24.15e3 for each of qs, ms, Ns, nus
-// es24.15e3 into exactly 24 characters (no terminator): one snprintf, exponent widened to three digits by hand
-static inline void put_es24(double v, char *out) {
-  char tmp[40];
-  if (std::isnan(v) || std::isinf(v)) {
-    char t[25];
-    srt_host::format_es24(v, t);
-    memcpy(out, t, 24);
-    return;
-  }
-  // [-]d.ddddddddddddddde+XX[X]: std::to_chars with a precision is correctly rounded like printf's %.15E (and 5x faster)
-  const std::to_chars_result tr = std::to_chars(tmp, tmp + sizeof tmp - 1, v, std::chars_format::scientific, 15);
-  const int n = (int)(tr.ptr - tmp);
-  tmp[n] = 0;
-  const char *e = (const char *)memchr(tmp, 'e', (size_t)n);
-  const int mant = (int)(e - tmp);
-  int ex = atoi(e + 2);
-  const int len = mant + 5;
-  char *q = out;
-  for (int k = len; k < 24; ++k) *q++ = ' ';
-  memcpy(q, tmp, (size_t)mant);
-  q += mant;
-  *q++ = 'E';
-  *q++ = e[1];
-  *q++ = (char)('0' + (ex / 100) % 10);
-  *q++ = (char)('0' + (ex / 10) % 10);
-  *q++ = (char)('0' + ex % 10);
-}
-
 // Records are fixed-length (raytracer_driver.f95:1197-1217: i10, i10, 17 es24.15e3, i10, 4 nspec es24.15e3, newline), so a
 // ray's file offset is known from the kept-row counts before it: all host cores format disjoint ray ranges and pwrite them
 // in place (SRT_IO_THREADS=1: one thread).  At BASELINE config[2] (1 M rays, 13 kept rows each) the file is 10.7 GB of text.
@@ -738,9 +898,8 @@ static int write_ray_records(const char *path, int append, int64_t raynum0, int6
                              const double *ms, const double *w0, const double *rows, const int32_t *stopcond,
                              const std::vector<int64_t> &prefix, size_t stride, size_t packed) {
   if (nspec < 1 || nspec > SRT_MAXSPEC) return srt_set_error(SRT_EINVAL, "nspec out of range");
-  // the record's ray number is an i10 field (raytracer_driver.f95:1197): beyond ten digits Fortran prints asterisks and the
-  // fixed-length record could not hold the number -- refused rather than shifted or truncated
-  if (raynum0 < 0 || nrays < 0 || raynum0 + nrays - 1 > 9999999999ll)
+  // the record's ray number is an i10 field (raytracer_driver.f95:1197)
+  if (nrays < 0 || !srt_host::fits_i10(raynum0, raynum0 + nrays - 1))
     return srt_set_error(SRT_EINVAL, "ray numbers %lld .. %lld do not fit the record's i10 field", (long long)raynum0, (long long)(raynum0 + nrays - 1));
   const size_t L = 20 + 17 * 24 + 10 + (size_t)4 * nspec * 24 + 1;
   const int fd = open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
@@ -845,9 +1004,7 @@ extern "C" int srt_write_ray_file_packed(const char *path, int append, int64_t r
                                          const double *ms, const double *w0, const int64_t *offsets, const double *rows,
                                          const int32_t *stopcond) {
   if (!path || !qs || !ms || !offsets || nrays < 0 || (nrays > 0 && (!w0 || !stopcond))) return srt_set_error(SRT_EINVAL, "null argument");
-  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
-  for (int64_t r = 0; r < nrays; ++r)
-    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "offsets decrease at ray %lld", (long long)r);
+  if (const int rc = srt_host::refuse_bad_offsets("", nrays, offsets)) return rc;
   if (offsets[nrays] > 0 && !rows) return srt_set_error(SRT_EINVAL, "null argument");
   const std::vector<int64_t> prefix(offsets, offsets + nrays + 1);
   return write_ray_records(path, append, raynum0, nrays, nspec, qs, ms, w0, rows, stopcond, prefix, 0, 1);
@@ -856,32 +1013,15 @@ extern "C" int srt_write_ray_file_packed(const char *path, int append, int64_t r
 // ---- event files: one record per event, (4 i10, then es24.15e3 fields): raynum, index + 1, interval + 1, meta[3], [distance,] the row ----
 static int write_event_records(const char *who, const char *path, int64_t nevents, const int64_t *raynum, const int32_t *event_meta,
                                const double *event_dist, const double *event_rows) {
-  for (int64_t e = 0; e < nevents; ++e)
-    if (raynum[e] < 0 || raynum[e] > 9999999999ll)
-      return srt_set_error(SRT_EINVAL, "%s: ray number %lld of event %lld does not fit the record's i10 field", who,
-                           (long long)raynum[e], (long long)e);
-  FILE *fp = fopen(path, "w");
-  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
-  std::vector<char> big(1 << 22);
-  setvbuf(fp, big.data(), _IOFBF, big.size());
-  const size_t L = 40 + (size_t)(SRT_ROW + (event_dist ? 1 : 0)) * 24 + 1;
-  std::vector<char> rec(L + 8);
-  for (int64_t e = 0; e < nevents; ++e) {
-    const int32_t *m = event_meta + 4 * e;
-    char head[48];
-    snprintf(head, sizeof head, "%10lld%10d%10d%10d", (long long)raynum[e], (int)m[1] + 1, (int)m[2] + 1, (int)m[3]);
-    memcpy(rec.data(), head, 40);
-    char *q = rec.data() + 40;
-    if (event_dist) {
-      put_es24(event_dist[e], q);
-      q += 24;
+  if (const int rc = srt_host::refuse_beyond_i10(who, "event", nevents, raynum)) return rc;
+  return srt_host::write_text(path, [&](TextWriter &t) {
+    for (int64_t e = 0; e < nevents; ++e) {
+      const int32_t *m = event_meta + 4 * e;
+      t.i10(raynum[e]).i10((long long)m[1] + 1).i10((long long)m[2] + 1).i10(m[3]);
+      if (event_dist) t.es24(event_dist[e]);
+      t.es24(event_rows + (size_t)e * SRT_ROW, SRT_ROW).end();
     }
-    for (int c = 0; c < SRT_ROW; ++c, q += 24) put_es24(event_rows[(size_t)e * SRT_ROW + c], q);
-    *q = '\n';
-    fwrite(rec.data(), 1, L, fp);
-  }
-  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
-  return SRT_OK;
+  });
 }
 
 // crossings file: (4 i10, 20 es24.15e3): raynum, surface + 1, interval + 1, direction, the row
@@ -905,35 +1045,17 @@ extern "C" int srt_approaches_file_write(const char *path, int64_t nevents, cons
 extern "C" int srt_tubes_file_write(const char *path, int64_t nrays, const int64_t *raynum, const int64_t *offsets, const double *rows,
                                     const double *section, const int32_t *flag) {
   if (!path || nrays < 0 || !offsets || (nrays > 0 && !raynum)) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: null argument");
-  if (offsets[0] != 0) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: offsets[0] = %lld: the first ray's rows start at 0", (long long)offsets[0]);
-  for (int64_t r = 0; r < nrays; ++r)
-    if (offsets[r + 1] < offsets[r]) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: offsets decrease at ray %lld", (long long)r);
+  if (const int rc = srt_host::refuse_bad_offsets("srt_tubes_file_write: ", nrays, offsets)) return rc;
   if (offsets[nrays] > 0 && (!rows || !section || !flag)) return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: null argument");
-  for (int64_t r = 0; r < nrays; ++r)
-    if (raynum[r] < 0 || raynum[r] > 9999999999ll)
-      return srt_set_error(SRT_EINVAL, "srt_tubes_file_write: ray number %lld of ray %lld does not fit the record's i10 field",
-                           (long long)raynum[r], (long long)r);
-  FILE *fp = fopen(path, "w");
-  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
-  std::vector<char> big(1 << 22);
-  setvbuf(fp, big.data(), _IOFBF, big.size());
-  const size_t L = 30 + 5 * 24 + 1;
-  char rec[L + 8];
-  for (int64_t r = 0; r < nrays; ++r)
-    for (int64_t j = offsets[r]; j < offsets[r + 1]; ++j) {
-      if (flag[j] == 1) continue;
-      char head[48];
-      snprintf(head, sizeof head, "%10lld%10lld%10d", (long long)raynum[r], (long long)(j - offsets[r] + 1), (int)flag[j]);
-      memcpy(rec, head, 30);
-      char *q = rec + 30;
-      put_es24(rows[(size_t)j * SRT_ROW], q);
-      q += 24;
-      for (int c = 0; c < 4; ++c, q += 24) put_es24(section[(size_t)j * 4 + c], q);
-      *q = '\n';
-      fwrite(rec, 1, L, fp);
-    }
-  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
-  return SRT_OK;
+  if (const int rc = srt_host::refuse_beyond_i10("srt_tubes_file_write", "ray", nrays, raynum)) return rc;
+  return srt_host::write_text(path, [&](TextWriter &t) {
+    for (int64_t r = 0; r < nrays; ++r)
+      for (int64_t j = offsets[r]; j < offsets[r + 1]; ++j) {
+        if (flag[j] == 1) continue;
+        t.i10(raynum[r]).i10(j - offsets[r] + 1).i10(flag[j]);
+        t.es24(rows[(size_t)j * SRT_ROW]).es24(section + (size_t)j * 4, 4).end();
+      }
+  });
 }
 
 // ---- bin file: a map of srt_bin_rays as text (include/srt.h) ----
@@ -950,30 +1072,14 @@ extern "C" int srt_bin_file_write(const char *path, const srt_bin_params *params
   int64_t ncells = 0;
   char why[200];
   if (bin_file_cells(params, &ncells, why, sizeof why)) return srt_set_error(SRT_EINVAL, "srt_bin_file_write: %s", why);
-  FILE *fp = fopen(path, "w");
-  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
-  std::vector<char> big(1 << 22);
-  setvbuf(fp, big.data(), _IOFBF, big.size());
-  char num[25];
-  num[24] = 0;
-  put_es24(params->quantum, num);
-  fprintf(fp, "%10d%10d%s\n", (int)params->naxes, (int)params->nsub, num);
-  for (int a = 0; a < params->naxes; ++a) {
-    fprintf(fp, "%10d%10d\n", (int)params->axis[a].kind, (int)params->axis[a].n);
-    for (int i = 0; i <= params->axis[a].n; ++i) {
-      put_es24(params->axis[a].edges[i], num);
-      fwrite(num, 1, 24, fp);
+  return srt_host::write_text(path, [&](TextWriter &t) {
+    t.i10(params->naxes).i10(params->nsub).es24(params->quantum).end();
+    for (int a = 0; a < params->naxes; ++a) {
+      t.i10(params->axis[a].kind).i10(params->axis[a].n).end();
+      t.es24(params->axis[a].edges, (size_t)params->axis[a].n + 1).end();
     }
-    fputc('\n', fp);
-  }
-  char rec[48];
-  for (int64_t c = 0; c < ncells; ++c) {
-    put_es24(ticks ? (double)ticks[c] * params->quantum : 0.0, rec);
-    snprintf(rec + 24, sizeof rec - 24, "%20lld\n", (long long)(hits ? hits[c] : 0));
-    fwrite(rec, 1, 45, fp);
-  }
-  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
-  return SRT_OK;
+    for (int64_t c = 0; c < ncells; ++c) t.es24(ticks ? (double)ticks[c] * params->quantum : 0.0).i20(hits ? hits[c] : 0).end();
+  });
 }
 
 extern "C" int srt_bin_file_read(const char *path, srt_bin_params *params, double **edges, int64_t *ncells, double **sum, int64_t **hits) {
@@ -1003,7 +1109,7 @@ extern "C" int srt_bin_file_read(const char *path, srt_bin_params *params, doubl
     at += (size_t)params->axis[a].n + 1;
     nedges += (size_t)params->axis[a].n + 1;
   }
-  double *ed = (double *)malloc(nedges * sizeof(double));
+  double *ed = copy_out<double>(nedges);
   if (!ed) return srt_set_error(SRT_ENOMEM, "bin file of %zu edges", nedges);
   size_t k = 0;
   for (int a = 0; a < params->naxes; ++a) {
@@ -1023,8 +1129,8 @@ extern "C" int srt_bin_file_read(const char *path, srt_bin_params *params, doubl
     return srt_set_error(SRT_EIO, "%s: bin file holds %zu values after its axes, its header announces %lld cells of two", path,
                          all.size() - at, (long long)nc);
   }
-  double *sm = (double *)malloc((size_t)nc * sizeof(double));
-  int64_t *hh = (int64_t *)malloc((size_t)nc * sizeof(int64_t));
+  double *sm = copy_out<double>((size_t)nc);
+  int64_t *hh = copy_out<int64_t>((size_t)nc);
   if (!sm || !hh) {
     free(ed), free(sm), free(hh);
     memset(params, 0, sizeof *params);
@@ -1053,21 +1159,11 @@ extern "C" int srt_dump_file_write(const char *path, int nspec, int nx, int ny, 
   if (!path || !bounds || !f) return srt_set_error(SRT_EINVAL, "null argument");
   if (nspec < 1 || nspec > SRT_MAXSPEC || nx < 1 || ny < 1 || nz < 1) return srt_set_error(SRT_EINVAL, "bad dump shape");
   const size_t n = (size_t)nx * ny * nz * (4 * (size_t)nspec + 3);
-  FILE *fp = fopen(path, "w");
-  if (!fp) return srt_set_error(SRT_EIO, "%s: cannot open for writing", path);
-  std::vector<char> big(1 << 22);
-  setvbuf(fp, big.data(), _IOFBF, big.size());
-  char num[25];
-  fprintf(fp, "%10d%10d%10d%10d\n", nspec, nx, ny, nz);
-  for (int k = 0; k < 6; ++k) { srt_host::format_es24(bounds[k], num); fputs(num, fp); }
-  fputc('\n', fp);
-  for (size_t c = 0; c < n; ++c) {
-    srt_host::format_es24(f[c], num);
-    num[24] = '\n';
-    fwrite(num, 1, 25, fp);
-  }
-  if (fclose(fp) != 0) return srt_set_error(SRT_EIO, "%s: write failed", path);
-  return SRT_OK;
+  return srt_host::write_text(path, [&](TextWriter &t) {
+    t.i10(nspec).i10(nx).i10(ny).i10(nz).end();
+    t.es24(bounds, 6).end();
+    for (size_t c = 0; c < n; ++c) t.es24(f[c]).end();
+  });
 }
 
 extern "C" int srt_dump_file_read(const char *path, int32_t dims[4], double bounds[6], double **f) {
@@ -1088,8 +1184,27 @@ extern "C" int srt_dump_file_read(const char *path, int32_t dims[4], double boun
                          all.size() - 10, dims[0], dims[1], dims[2], dims[3], want);
   for (int k = 0; k < 6; ++k) bounds[k] = all[4 + k];
   const size_t n = all.size() - 10;
-  *f = (double *)malloc(n * sizeof(double));
+  *f = copy_out(n, all.data() + 10);
   if (!*f) return srt_set_error(SRT_ENOMEM, "dump of %zu values", n);
-  memcpy(*f, all.data() + 10, n * sizeof(double));
   return SRT_OK;
+}
+
+// ---- model-4 sample files (include/srt.h) ----
+extern "C" int srt_points_file_write(const char *path, int binary, int nspec, int64_t npts, const double bounds[6], const double *qs,
+                                     const double *ms, const double *records) {
+  if (!path || !bounds || !qs || !ms || (npts > 0 && !records) || npts < 0) return srt_set_error(SRT_EINVAL, "bad argument");
+  if (nspec < 1 || nspec > SRT_MAXSPEC) return srt_set_error(SRT_EINVAL, "nspec=%d unsupported", nspec);
+  return srt_host::write_points_file(path, binary != 0, nspec, npts, bounds, qs, ms, records);
+}
+extern "C" int srt_points_file_is_binary(const char *path) { return path && srt_host::has_magic(path, srt_host::PTS_MAGIC) ? 1 : 0; }
+extern "C" int srt_points_file_convert(const char *in, const char *out_binary) {
+  if (!in || !out_binary) return srt_set_error(SRT_EINVAL, "null argument");
+  std::vector<double> all;
+  std::string err;
+  if (srt_host::has_magic(in, srt_host::PTS_MAGIC)) return srt_set_error(SRT_EINVAL, "%s is already binary", in);
+  if (!srt_host::read_all_numbers(in, all, err) || all.size() < 7) return srt_set_error(SRT_EIO, "%s: %s", in, err.empty() ? "too short" : err.c_str());
+  srt_host::PointsText p;
+  if (!srt_host::split_points_text(all, p))
+    return srt_set_error(SRT_EIO, "%s: not a model-4 sample file (or records do not match their READs)", in);
+  return srt_host::write_points_file(out_binary, true, p.nspec, p.npts, p.bounds, p.qs, p.ms, p.rec);
 }

@@ -36,10 +36,6 @@ struct GridFile {
 };
 // text (parsed by all host cores) or the binary side-format "SRTGRID1" (detected by its magic)
 bool read_grid_file(const char *path, GridFile &g, std::string &err);
-bool is_binary_grid(const char *path);
-// binary side-format: 144-byte header {magic, compder, nspec, nx, ny, nz, bounds[6], qs[4], ms[4]} followed by the
-// value blocks of the text format as raw little-endian doubles in the same order
-bool write_grid_binary(const char *path, const GridFile &g, std::string &err);
 
 // Fortran list-directed numeric reader: a READ starts on a new record and continues over following
 // records until its list is satisfied; blanks and commas separate; 'd' exponents accepted.
@@ -55,21 +51,17 @@ private:
   std::vector<char> line_;
 };
 
-// every numeric token of a text file in order, parsed by all host cores
-bool read_all_numbers(const char *path, std::vector<double> &all, std::string &err);
-
-// es24.15e3 edit descriptor
-void format_es24(double v, char out[25]);
+// model-4 sample file (scattered_interp_dens_model_adapter.f95:85-133), text (parsed by all host cores where every record
+// holds what its READ takes, else READ by READ) or the binary side-format "SRTPTS01" (detected by its magic): the species
+// and the records [npts][3 + nspec]
+bool read_points_file(const char *path, int &nspec, double qs[4], double ms[4], std::vector<double> &rec, std::string &err);
 
 } // namespace srt_host
 
 namespace srt_host {
-// model-4 scattered sample file (scattered_interp_dens_model_adapter.f95:85-133) prepared for the device:
+// model-4 scattered sample file prepared for the device:
 // duplicates dropped (:160-163), nearest-sample distance per sample outside the Earth (:167-203),
 // samples binned into a uniform grid with cell edge = maxnearest*window_scale and sorted by cell.
-bool is_binary_points(const char *path);
-bool write_points_file(const char *path, bool binary, int nspec, int64_t npts, const double bounds[6], const double *qs, const double *ms,
-                       const double *rec, std::string &err);
 struct ScatteredHost {
   int nspec = 0, npts = 0;
   double qs[4] = {0}, ms[4] = {0};
